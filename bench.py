@@ -8,7 +8,12 @@ snapshot (``ks_restore`` of a device-side checkpoint), the pods' PreFilter / Est
 (``prep_pods_kernel``), then the sweep -> select -> commit passes.  The raw pod columns are staged in HBM
 before the timed region (host -> HBM copies are not timed; everything computed from them is).
 
-The metric names 5k AND 100k nodes, so the same line carries ``c5``: configs[4] (1M pods x 100k nodes,
+A plain run (``--gpus 1 --steps N --warmup W``) does only that: set up, W warm-up steps, the N timed steps, the
+``--dump-outputs DIR`` files if asked for (the result columns of the last timed step, DIR/<name>.npy), and the line.
+Everything below — the other records, the profiled steps behind the kernel split and the rooflines, the CPU
+baselines and sample parity — is run with ``--full``.
+
+The metric names 5k AND 100k nodes, so with ``--full`` the same line carries ``c5``: configs[4] (1M pods x 100k nodes,
 Fit + LoadAware) timed the same way — on one GPU at N=1, node-sharded over the N ranks at N>1 (strong
 scaling: every rank sweeps its node range, one RCCL allgather of per-shard candidates per pass).
 At N=1 it also carries ``c3`` (configs[2]: NUMA + DeviceShare joint allocation, 5k nodes), ``c4`` (configs[3]:
@@ -273,6 +278,10 @@ def run_config(w, args, dist, world: int, rank: int, local_rank: int, shard: boo
         sync()
         elapsed = time.perf_counter() - t0
         st_last = ev.stats()
+        # what a caller of the timed path receives after its last step (read before the profiled steps re-run it)
+        res = ev.fetch()
+        if w.cpus is not None:
+            res["cpusets"] = ev.fetch_cpusets(w.pods.n)
         agg = {"sweep_ms": 0.0, "select_ms": 0.0, "commit_ms": 0.0, "fixup_ms": 0.0, "sweep_launches": 0, "passes": 0,
                "cut_passes": 0, "rescans": 0, "bubble_passes": 0, "pre_reserves": 0}
         prof_elapsed = 0.0
@@ -298,9 +307,6 @@ def run_config(w, args, dist, world: int, rank: int, local_rank: int, shard: boo
             t = torch.tensor([elapsed], dtype=torch.float64, device=f"cuda:{local_rank}")
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             elapsed = float(t.item())
-        res = ev.fetch()
-        if w.cpus is not None:
-            res["cpusets"] = ev.fetch_cpusets(w.pods.n)
     finally:
         ev.close()
 
@@ -470,6 +476,32 @@ def run_preempt(args, steps: int, warmup: int, profile: bool, cpu: bool):
     return rec
 
 
+DUMP_MAX_BYTES = 64 << 20
+DUMP_SEED = 20261015
+
+
+def dump_outputs(res: dict, out_dir: str) -> None:
+    """--dump-outputs: the result columns of the last timed step (what Evaluator.fetch / fetch_cpusets hand a caller:
+    one row per pod) as <out_dir>/<name>.npy in float64.  Every column here is an integer below 2^53 except the cpuset
+    words (uint64 bit masks), which are written as their little-endian 32-bit halves, so float64 holds all of them
+    exactly.  Above 64 MB in all, the same seeded sample of pod rows (ascending, in `rows.npy`) is kept of every column."""
+    os.makedirs(out_dir, exist_ok=True)
+    cols = {}
+    for k, v in res.items():
+        v = np.ascontiguousarray(v)
+        if v.dtype == np.uint64:
+            v = v.view("<u4")
+        cols[k] = v.astype(np.float64)
+    n = len(next(iter(cols.values())))
+    row_bytes = sum(c.nbytes // max(n, 1) for c in cols.values()) + 8
+    if n * row_bytes > DUMP_MAX_BYTES:
+        rows = np.sort(np.random.default_rng(DUMP_SEED).choice(n, DUMP_MAX_BYTES // row_bytes, replace=False))
+        cols = {k: c[rows] for k, c in cols.items()}
+        cols["rows"] = rows.astype(np.float64)
+    for k, c in cols.items():
+        np.save(os.path.join(out_dir, f"{k}.npy"), c)
+
+
 def workload_desc(w):
     return (f"{w.name}: {w.pods.n} pods x {w.nodes.n} nodes, NodeResourcesFit(LeastAllocated cpu/mem/batch-cpu/batch-mem)"
             f" + LoadAwareScheduling(defaults)" + (" + ElasticQuota(32 leaf quotas)" if w.quotas is not None else "")
@@ -491,8 +523,14 @@ def main():
     ap.add_argument("--pods", type=int, default=0, help="pods per step (default: the config's own count)")
     ap.add_argument("--batch-pods", type=int, default=0)
     ap.add_argument("--candidates", type=int, default=0)
-    ap.add_argument("--no-profile", action="store_true", help="do not bracket kernels with HIP events")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline's timed steps also run everything else the line can carry: the profiled "
+                         "steps (kernel split, roofline), the CPU baselines with sample parity, and the c5 / sub-workload "
+                         "/ preempt / replica records (each can be dropped again with its --no-* option)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write the result columns of the last timed step of the main config as DIR/<name>.npy (float64)")
+    ap.add_argument("--no-profile", action="store_true", help="with --full: do not bracket kernels with HIP events")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: no CPU oracle runs")
     ap.add_argument("--cpu-budget-s", type=float, default=15.0, help="16-thread oracle sample (per config)")
     ap.add_argument("--cpu-extra-budget-s", type=float, default=6.0, help="1-thread / all-core oracle samples")
     ap.add_argument("--replicas", action="store_true",
@@ -518,6 +556,12 @@ def main():
         print(json.dumps({"preempt": rec}), flush=True)
         return
 
+    # a plain run times the main config and nothing else; --full adds the other records and measurements
+    profile = args.full and not args.no_profile
+    cpu = args.full and not args.no_cpu_baseline
+    if not args.full:
+        args.no_c5 = args.no_sub = True
+
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -533,9 +577,11 @@ def main():
     # replicas schedule their own cluster (seed + rank); shards split one shared cluster
     w = build_workload(args.config, seed=20261015 + (0 if args.shard else rank), n_pods=args.pods)
     rec, res = run_config(w, args, dist, world, rank, local_rank, args.shard, args.steps, args.warmup, args.config,
-                          not args.no_profile)
+                          profile)
     out = None
     if rank == 0:
+        if args.dump_outputs:
+            dump_outputs(res, args.dump_outputs)
         out = {
             "metric": METRIC,
             "value": rec["value"],
@@ -559,7 +605,7 @@ def main():
         }
         out.update({k: v for k, v in rec.items() if k not in ("value", "unit", "ms_per_step", "steps", "warmup")})
         out["cpu_baseline"] = None
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and cpu:
             cb = cpu_baseline(w, res, args.cpu_budget_s, args.cpu_extra_budget_s)
             out["cpu_baseline"] = cb
             out["parity"] = cb["parity_with_gpu_on_sample"]
@@ -580,12 +626,12 @@ def main():
         # the metric's 100k-node configuration: one GPU at N=1, node-sharded over the ranks at N>1
         w5 = build_workload("c5", seed=20261015, n_pods=args.c5_pods)
         r5, res5 = run_config(w5, args, dist, world, rank, local_rank, True, args.c5_steps, args.c5_warmup, "c5",
-                              not args.no_profile)
+                              profile)
         if rank == 0:
             r5["workload"] = workload_desc(w5)
             r5["scaling"] = "strong"
             r5["parallelism"] = f"node-shards{world}" if world > 1 else "single-gpu"
-            if world == 1 and not args.no_cpu_baseline:
+            if world == 1 and cpu:
                 cb5 = cpu_baseline(w5, res5, args.cpu_budget_s, args.cpu_extra_budget_s)
                 r5["cpu_baseline"] = cb5
                 r5["parity"] = cb5["parity_with_gpu_on_sample"]
@@ -600,11 +646,10 @@ def main():
         # those two (the round-4 c2d)
         for sub in ("c3", "c4", "c2d", "c2s", "c3r", "c3rd"):
             ws = build_workload(sub, seed=20261015)
-            rs, ress = run_config(ws, args, None, 1, 0, 0, False, args.sub_steps, args.sub_warmup, sub,
-                                  not args.no_profile)
+            rs, ress = run_config(ws, args, None, 1, 0, 0, False, args.sub_steps, args.sub_warmup, sub, profile)
             rs["workload"] = workload_desc(ws)
             rs["parallelism"] = "single-gpu"
-            if not args.no_cpu_baseline:
+            if cpu:
                 cbs = cpu_baseline(ws, ress, args.cpu_budget_s, args.cpu_extra_budget_s)
                 rs["cpu_baseline"] = cbs
                 rs["parity"] = cbs["parity_with_gpu_on_sample"]
@@ -612,7 +657,7 @@ def main():
             out[sub] = rs
             del ws, ress
     if not args.no_sub and not args.no_preempt and world == 1 and args.config == "c2":
-        out["preempt"] = run_preempt(args, args.sub_steps, args.sub_warmup, not args.no_profile, not args.no_cpu_baseline)
+        out["preempt"] = run_preempt(args, args.sub_steps, args.sub_warmup, profile, cpu)
     if dist is not None:
         dist.barrier()
         dist.destroy_process_group()

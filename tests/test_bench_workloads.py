@@ -18,3 +18,22 @@ def test_c3rd_is_the_parity_tests_workload():
     assert np.array_equal(w.reservations.dev_allocatable, ref.reservations.dev_allocatable)
     held = (w.reservations.dev_allocatable != 0).any(axis=1)
     assert 0.3 < held.mean() < 0.35
+
+
+def test_dump_outputs_is_exact_and_bounded(tmp_path, monkeypatch):
+    n = 300
+    res = {"node": np.arange(n, dtype="<i4") - 1, "score": np.arange(n, dtype="<i8") * 10**12,
+           "cpusets": np.full((n, 4), 2**63 + 5, np.uint64)}
+    bench.dump_outputs(res, str(tmp_path / "all"))
+    got = {k: np.load(tmp_path / "all" / f"{k}.npy") for k in res}
+    assert all(a.dtype == np.float64 for a in got.values())
+    assert np.array_equal(got["node"].astype("<i4"), res["node"]) and np.array_equal(got["score"].astype("<i8"), res["score"])
+    assert np.array_equal(got["cpusets"].astype("<u4").view(np.uint64), res["cpusets"])  # 32-bit halves, little-endian
+    # above the size limit: one seeded sample of pod rows for every column, the same from run to run
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 4000)
+    for d in ("s1", "s2"):
+        bench.dump_outputs(res, str(tmp_path / d))
+    rows = np.load(tmp_path / "s1" / "rows.npy").astype(np.int64)
+    assert 0 < len(rows) < n and np.array_equal(rows, np.load(tmp_path / "s2" / "rows.npy"))
+    assert sum((tmp_path / "s1" / f).stat().st_size - 128 for f in ("rows.npy", "node.npy", "score.npy", "cpusets.npy")) <= 4000
+    assert np.array_equal(np.load(tmp_path / "s1" / "score.npy"), res["score"][rows].astype(np.float64))

@@ -12,7 +12,7 @@ for r in 1 2; do
     steps=5; [ "$c" = c5 ] && steps=2
     for side in A B; do
       dir=.; [ $side = B ] && dir=$ALT
-      timeout -k 10 300 python -u $dir/bench.py --config $c --no-c5 --no-sub --no-cpu-baseline --steps $steps \
+      timeout -k 10 300 python -u $dir/bench.py --full --config $c --no-c5 --no-sub --no-cpu-baseline --steps $steps \
         --warmup 1 > $OUT/${c}_${side}_$r.json 2> $OUT/${c}_${side}_$r.err || { tail -5 $OUT/${c}_${side}_$r.err; exit 1; }
     done
     python3 -c "import json;a=json.load(open('$OUT/${c}_A_$r.json'));b=json.load(open('$OUT/${c}_B_$r.json'));print('$c r$r A',a['value'],a['ms_per_step'],'B',b['value'],b['ms_per_step'])"

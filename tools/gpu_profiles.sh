@@ -15,7 +15,7 @@ for CFG in ${CONFIGS:-c2 c3 c4 c2d c2s c3r c3rd}; do
   # (c2d: the topology loop without its HIP graph -- rocprofv3's CSV kernel trace of the captured loop died in the
   # HIP runtime in round 5)
   G=1; [ "$CFG" = c2d ] && G=0
-  KS_TOPO_GRAPH=$G timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_$CFG -o run -- python3 bench.py --config $CFG --no-c5 --no-sub --no-cpu-baseline > $OUT/prof_$CFG.json 2> $OUT/prof_$CFG.err || { echo "rocprof $CFG failed"; tail -30 $OUT/prof_$CFG.err; exit 1; }
+  KS_TOPO_GRAPH=$G timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_$CFG -o run -- python3 bench.py --full --config $CFG --no-c5 --no-sub --no-cpu-baseline > $OUT/prof_$CFG.json 2> $OUT/prof_$CFG.err || { echo "rocprof $CFG failed"; tail -30 $OUT/prof_$CFG.err; exit 1; }
   S=$(find $OUT/prof_$CFG -name '*kernel_stats.csv' | head -1)
   [ -n "$S" ] && cp $S $OUT/${CFG}_kernel_stats.csv
   rm -rf $OUT/prof_$CFG
@@ -45,7 +45,7 @@ if [ "${C5:-1}" = 1 ]; then
   KS_PIPE=0 BENCH_ARGS="--no-c5 --pods 200000" bash tools/pmc_valu.sh c5 ${OUT#gpurun_out/}/valu_c5 > /dev/null || exit 1
   cp $OUT/valu_c5/valu.json $OUT/c5_valu.json
   rm -rf $OUT/traffic_c5 $OUT/valu_c5
-  timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_c5 -o run -- python3 bench.py --config c5 --no-c5 --no-cpu-baseline --pods 200000 --steps 2 --warmup 1 > $OUT/prof_c5.json 2> $OUT/prof_c5.err
+  timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_c5 -o run -- python3 bench.py --full --config c5 --no-c5 --no-cpu-baseline --pods 200000 --steps 2 --warmup 1 > $OUT/prof_c5.json 2> $OUT/prof_c5.err
   rc=$?
   S=$(find $OUT/prof_c5 -name '*kernel_stats.csv' | head -1)
   [ -n "$S" ] && cp $S $OUT/c5_kernel_stats.csv

@@ -9,6 +9,6 @@ tail -3 $OUT/pytest_gpu.log
 timeout -k 10 300 python -u -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke.log 2>&1 || { echo "smoke failed"; tail -30 $OUT/smoke.log; exit 1; }
 cat $OUT/smoke.log
 if [ "${BENCH:-0}" = 1 ]; then
-  timeout -k 10 400 python -u bench.py ${BENCH_ARGS:---no-c5 --no-cpu-baseline} --detail $OUT/bench_detail.json > $OUT/bench.json 2> $OUT/bench.err || { tail -30 $OUT/bench.err; exit 1; }
+  timeout -k 10 400 python -u bench.py --full ${BENCH_ARGS:---no-c5 --no-cpu-baseline} --detail $OUT/bench_detail.json > $OUT/bench.json 2> $OUT/bench.err || { tail -30 $OUT/bench.err; exit 1; }
   python3 tools/bench_summary.py $OUT/bench.json
 fi

@@ -9,6 +9,6 @@ export TMPDIR=/tmp
 # CFG=preempt: the bench's preempt record alone (bench.py --preempt-only)
 if [ "$CFG" = preempt ]; then SEL="--preempt-only"; else SEL="--config $CFG"; fi
 for C in FETCH_SIZE WRITE_SIZE; do
-  timeout -s KILL 180 rocprofv3 --pmc $C --output-format csv -d $OUT/$C -o pmc -- python3 bench.py $SEL --steps 1 --warmup 0 --no-cpu-baseline ${BENCH_ARGS} > $OUT/$C.log 2>&1 || { echo "pmc $C failed"; tail -5 $OUT/$C.log; exit 1; }
+  timeout -s KILL 180 rocprofv3 --pmc $C --output-format csv -d $OUT/$C -o pmc -- python3 bench.py --full $SEL --steps 1 --warmup 0 --no-cpu-baseline ${BENCH_ARGS} > $OUT/$C.log 2>&1 || { echo "pmc $C failed"; tail -5 $OUT/$C.log; exit 1; }
 done
 python3 tools/traffic.py $OUT $CFG > $OUT/traffic.json && cat $OUT/traffic.json

@@ -9,5 +9,5 @@ mkdir -p $OUT
 export TMPDIR=/tmp
 timeout -s KILL 60 rocprofv3 -L > $OUT/counters.txt 2>&1 || true
 timeout -s KILL 240 rocprofv3 --pmc SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_ANY SQ_WAVE_CYCLES SQ_WAIT_INST_ANY SQ_WAIT_ANY GRBM_GUI_ACTIVE \
-  --output-format csv -d $OUT/pmc -o pmc -- python3 bench.py --config $CFG --steps 1 --warmup 0 --no-cpu-baseline ${BENCH_ARGS} > $OUT/pmc.log 2>&1 || { echo "pmc failed"; tail -5 $OUT/pmc.log; exit 1; }
+  --output-format csv -d $OUT/pmc -o pmc -- python3 bench.py --full --config $CFG --steps 1 --warmup 0 --no-cpu-baseline ${BENCH_ARGS} > $OUT/pmc.log 2>&1 || { echo "pmc failed"; tail -5 $OUT/pmc.log; exit 1; }
 python3 tools/valu.py $OUT/pmc $CFG $3 > $OUT/valu.json && cat $OUT/valu.json
