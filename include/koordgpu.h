@@ -752,7 +752,12 @@ typedef struct ks_ctx ks_ctx;
 int ks_abi_layout(int64_t *out, int32_t n);
 
 /* Returns KS_OK and *out on success.  On failure *out is NULL and
- * ks_last_error(NULL) describes the problem. */
+ * ks_last_error(NULL) describes the problem.
+ * Environment switches read here, once per context (the others -- KS_COMMIT_GENERAL, KS_PIPE, KS_PIPE_MIN_NODES,
+ * KS_SWEEP_PPW, KS_SWEEP_BLOCK_CAP, INTEGRATION.md §4 -- are read once per process):
+ *   KS_COMMIT_FQ=0  a monotone Fit (LeastAllocated) + LoadAware + ElasticQuota context commits with the general
+ *                   commit kernel instead of the dedicated one (ks_fq.h).  Results are identical; the switch is
+ *                   for A/B timing and for tests that compare the two kernels from one process. */
 int ks_create(const ks_config *cfg, ks_ctx **out);
 void ks_destroy(ks_ctx *ctx);
 const char *ks_last_error(const ks_ctx *ctx);

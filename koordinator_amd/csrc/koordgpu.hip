@@ -33,6 +33,7 @@
 
 #include "ks_pass.h"
 #include "ks_mono.h"
+#include "ks_fq.h"
 #include "ks_debug.h"
 #include "ks_topo.h"
 #include "ks_preempt.h"
@@ -262,6 +263,7 @@ __global__ __launch_bounds__(kSelThreads) void select_kernel(SelectArgs a) {
   // XCD-aware pod placement (blocks are dealt round-robin over the 8 XCDs): the 16 pods whose words share a 128-B line
   // of a chunk row run on one XCD, so each line is fetched into one L2 once, not by every XCD (kSelBlocks blocks, those
   // of XCDs 4-7 idle)
+  static_assert(kMaxBatch == 64, "the XCD mapping below: 4 XCDs x 16 pods (and ks_fq.h's per-pod records)");
   const int32_t xcd = (int32_t)(blockIdx.x & 7u);
   if (xcd >= kMaxBatch / 16) return;
   const int32_t p = xcd * 16 + (int32_t)(blockIdx.x >> 3);
@@ -1111,6 +1113,7 @@ struct ks_ctx {
   hipEvent_t pev_com[kPipeEvents] = {};
   int64_t pipe_k = 0;               // pass index within the current ks_schedule* call
   int32_t pipe_mode = -1;           // ks_set_pipeline (-1: KS_PIPE, default automatic)
+  bool commit_fq = true;            // KS_COMMIT_FQ at ks_create: the dedicated Fit + LoadAware + ElasticQuota commit (ks_fq.h)
   // preemption (ks_load_node_pods / ks_preempt, ks_preempt.h)
   void* npod_blob = nullptr;       // the node-pod table (positions sorted per node) + per-call scratch
   DevNodePods npt{};
@@ -1379,6 +1382,7 @@ int ks_create(const ks_config* cfg, ks_ctx** out) {
   ctx->device = cfg->device;
   ctx->batch = cfg->batch_pods > 0 ? std::min(cfg->batch_pods, kMaxBatch) : 64;
   ctx->k = cfg->candidates > 0 ? std::min(cfg->candidates, kMaxCand) : 32;
+  ctx->commit_fq = env_i64("KS_COMMIT_FQ", 1, 0, 1) != 0;  // (per context: a process can build one of each, tests / A-B)
   if (hipSetDevice(ctx->device) != hipSuccess || hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking) != hipSuccess) {
     g_create_error = "ks_create: cannot create HIP stream";
     delete ctx;
@@ -3650,7 +3654,8 @@ static CommitArgs commit_args(ks_ctx* ctx, PodStage& st, int32_t total, int32_t 
 
 // The monotone commit kernel (ks_mono.h) runs the passes of a plugin set without Reservation, NodeNUMAResource or
 // DeviceShare whose keys commits can only lower (Fit LeastAllocated + LoadAware) when its LDS fits.  With
-// ElasticQuota the general kernel runs instead: its admission look-ahead for pod j + 1 overlaps pod j's Reserve,
+// ElasticQuota the general kernel's pass runs instead (as ks_fq.h's dedicated kernel when the quota tables fit the
+// LDS, fq_commit below): its admission look-ahead for pod j + 1 overlaps pod j's Reserve,
 // and that measured faster than the mono kernel's prebuilt rows at C2 (MI355X, commit 20.6 vs 21.4 ms/step;
 // C5 without quota: mono 275.6 vs general 281.3 ms per 200k pods, profiles/r02_commit_ab.txt).
 // KS_COMMIT_GENERAL=1 keeps the general kernel, =2 forces the mono kernel with quota too (A/B).  ks_assume always
@@ -3662,6 +3667,18 @@ static bool mono_commit(const ks_ctx* ctx, bool qcache, size_t* smem) {
   *smem = mono_layout(ctx->k, ctx->nchunks, qcache, ctx->q.q).total;
   return *smem <= 160 * 1024;
 }
+
+// The dedicated commit kernel of the monotone Fit (LeastAllocated) + LoadAware + ElasticQuota plugin set (ks_fq.h)
+// runs exactly where commit_kernel<NSC, true, 0> would run for a monotone profile: quota tables in LDS, no
+// Reservation / NUMA / DeviceShare / dictionary plugins, not the patched pipeline (its lists can hold emptied
+// chunks and its tops are rebuilt).  KS_COMMIT_FQ=0, read when the context is created, keeps the general kernel
+// (A/B, tests).  Same CommitArgs and LDS layout as the general kernel.
+static bool fq_commit(const ks_ctx* ctx, bool qcache, bool patch) {
+  return ctx->commit_fq && qcache && !patch && kernel_feat(ctx) == 0 && ctx->kc.monotone && !ctx->kc.fit_most &&
+         ctx->kc.quota_enable;
+}
+
+static FqLaunch fq_launcher(int nsc) { return nsc == 0 ? fq_launch_n0() : (nsc == 2 ? fq_launch_n2() : fq_launch_n4()); }
 
 // Reserve's NodeNUMAResource / DeviceShare allocations ahead of the commit (reserve_pre_kernel): on for
 // the NUMA topology policy variants when policy nodes are loaded; KS_PRE_RSV=0 turns it off (A/B).
@@ -3680,6 +3697,10 @@ static int commit_attr_set(ks_ctx* ctx) {
     KS_FAIL(ctx, KS_EUNSUPPORTED, "too many nodes for the commit kernel's LDS (%lld nodes, %zu B)", (long long)ctx->n, smem);
   hipError_t e = pass_launcher(kernel_feat(ctx), ctx->nsc).commit_attr(qcache, smem);
   if (e != hipSuccess) KS_FAIL(ctx, KS_EHIP, "hipFuncSetAttribute(commit LDS %zu): %s", smem, hipGetErrorString(e));
+  if (fq_commit(ctx, qcache, false)) {
+    e = fq_launcher(ctx->nsc).commit_attr(smem);
+    if (e != hipSuccess) KS_FAIL(ctx, KS_EHIP, "hipFuncSetAttribute(fq commit LDS %zu): %s", smem, hipGetErrorString(e));
+  }
   size_t msmem = 0;
   if (mono_commit(ctx, qcache, &msmem)) {
     e = pass_launcher(0, ctx->nsc).commit_mono_attr(qcache, msmem);
@@ -4274,6 +4295,7 @@ static int launch_pass(ks_ctx* ctx, int32_t ppw, int sweep_blocks, const PipeSha
   rec(2, cs);
   if (ca.pre_rsv) HIPCHK(ctx, pl.reserve_pre(ctx->batch, cs, ca));  // (timed with the commit)
   if (mono) HIPCHK(ctx, pl.commit_mono(qcache, msmem, cs, ca));
+  else if (fq_commit(ctx, qcache, patch)) HIPCHK(ctx, fq_launcher(ctx->nsc).commit(smem, cs, ca));
   else HIPCHK(ctx, pl.commit(qcache, smem, cs, ca));
   rec(2, cs);
   if (pipe) HIPCHK(ctx, hipEventRecord(ctx->pev_com[k % kPipeEvents], cs));

@@ -2,6 +2,7 @@
 // wrappers.  The Makefile compiles this file once per (FEAT, NSC) so the variants build in parallel.
 #include "ks_pass.h"
 #include "ks_mono.h"
+#include "ks_fq.h"
 
 #if !defined(KS_FEAT) || !defined(KS_NSC)
 #error "compile with -DKS_FEAT=<feature bits> -DKS_NSC=<0|2|4>"
@@ -45,6 +46,16 @@ hipError_t commit_mono_attr(bool qc, size_t smem) {
   const void* fn = qc ? (const void*)commit_mono_kernel<NSC, true> : (const void*)commit_mono_kernel<NSC, false>;
   return hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
 }
+
+// the monotone Fit + LoadAware + ElasticQuota commit with the quota tables in LDS (ks_fq.h)
+hipError_t commit_fq(size_t smem, hipStream_t s, const CommitArgs& a) {
+  hipLaunchKernelGGL((commit_fq_kernel<NSC>), dim3(1), dim3(commit_threads(0)), smem, s, a);
+  return hipGetLastError();
+}
+
+hipError_t commit_fq_attr(size_t smem) {
+  return hipFuncSetAttribute((const void*)commit_fq_kernel<NSC>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
+}
 #endif
 
 #if (KS_FEAT & 8) != 0
@@ -65,5 +76,9 @@ PassLaunch KS_CAT(KS_CAT(KS_CAT(pass_launch_f, KS_FEAT), _n), KS_NSC)() {
   return PassLaunch{sweep, commit, commit_attr, nullptr, nullptr, nullptr};
 #endif
 }
+
+#if KS_FEAT == 0
+FqLaunch KS_CAT(fq_launch_n, KS_NSC)() { return FqLaunch{commit_fq, commit_fq_attr}; }
+#endif
 
 }  // namespace ks
