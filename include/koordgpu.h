@@ -686,7 +686,9 @@ typedef struct ks_stats {
                               (the pod's node ranked in its snapshot top) */
   int64_t commit_lds_bytes; /* the commit kernel's LDS image for this context (of the CU's 160 KB) */
   int64_t commit_helpers;   /* 1 = the NUMA-policy + DeviceShare commit ran its helper waves (their region fit the LDS
-                               next to the slot caches; 0 = wave 0 computed the device hints itself) */
+                               next to the slot caches; 0 = wave 0 computed the device hints itself);
+                               2 = the Fit + LoadAware + ElasticQuota commit ran its slot-key evaluator wave (the key
+                               table fit the LDS and KS_FQ_KEYS was not 0; commit_lds_bytes includes the table) */
 } ks_stats;
 
 /* ---- preemption: the ElasticQuota PostFilter ----
@@ -757,7 +759,11 @@ int ks_abi_layout(int64_t *out, int32_t n);
  * KS_SWEEP_PPW, KS_SWEEP_BLOCK_CAP, INTEGRATION.md §4 -- are read once per process):
  *   KS_COMMIT_FQ=0  a monotone Fit (LeastAllocated) + LoadAware + ElasticQuota context commits with the general
  *                   commit kernel instead of the dedicated one (ks_fq.h).  Results are identical; the switch is
- *                   for A/B timing and for tests that compare the two kernels from one process. */
+ *                   for A/B timing and for tests that compare the two kernels from one process.
+ *   KS_FQ_KEYS=0    the dedicated kernel evaluates a slow pod's keys on the touched slots in its sequential wave
+ *                   (lane = slot) instead of reading them from the slot-key table its evaluator wave fills (the
+ *                   default when the table fits the commit's LDS image; ks_stats.commit_helpers == 2 says it ran).
+ *                   Results and counters are identical; for A/B timing and tests. */
 int ks_create(const ks_config *cfg, ks_ctx **out);
 void ks_destroy(ks_ctx *ctx);
 const char *ks_last_error(const ks_ctx *ctx);

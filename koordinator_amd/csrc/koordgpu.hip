@@ -1114,6 +1114,7 @@ struct ks_ctx {
   int64_t pipe_k = 0;               // pass index within the current ks_schedule* call
   int32_t pipe_mode = -1;           // ks_set_pipeline (-1: KS_PIPE, default automatic)
   bool commit_fq = true;            // KS_COMMIT_FQ at ks_create: the dedicated Fit + LoadAware + ElasticQuota commit (ks_fq.h)
+  bool fq_keys = true;              // KS_FQ_KEYS at ks_create: that kernel's slot-key table and evaluator wave
   // preemption (ks_load_node_pods / ks_preempt, ks_preempt.h)
   void* npod_blob = nullptr;       // the node-pod table (positions sorted per node) + per-call scratch
   DevNodePods npt{};
@@ -1383,6 +1384,7 @@ int ks_create(const ks_config* cfg, ks_ctx** out) {
   ctx->batch = cfg->batch_pods > 0 ? std::min(cfg->batch_pods, kMaxBatch) : 64;
   ctx->k = cfg->candidates > 0 ? std::min(cfg->candidates, kMaxCand) : 32;
   ctx->commit_fq = env_i64("KS_COMMIT_FQ", 1, 0, 1) != 0;  // (per context: a process can build one of each, tests / A-B)
+  ctx->fq_keys = env_i64("KS_FQ_KEYS", 1, 0, 1) != 0;
   if (hipSetDevice(ctx->device) != hipSuccess || hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking) != hipSuccess) {
     g_create_error = "ks_create: cannot create HIP stream";
     delete ctx;
@@ -3678,6 +3680,19 @@ static bool fq_commit(const ks_ctx* ctx, bool qcache, bool patch) {
          ctx->kc.quota_enable;
 }
 
+// The dedicated kernel's slot-key table (ks_fq.h, KEYS = true): a slow pod's keys on the touched slots come from the
+// evaluator wave's LDS table instead of wave 0's own lane = slot evaluation.  On when the commit image still fits the
+// CU's LDS with the table (C2: candidates = 32; not with candidates = 64); otherwise, and with KS_FQ_KEYS=0 (read
+// when the context is created: A/B, tests), wave 0 evaluates as before.  *smem: the image with the table.
+static bool fq_keys(const ks_ctx* ctx, bool qcache, bool patch, size_t* smem) {
+  if (!ctx->fq_keys || !fq_commit(ctx, qcache, patch)) return false;
+  const size_t t = commit_layout(ctx->k, ctx->nchunks, true, 0, dev_cache_bytes(ctx), numa_cache_bytes(ctx), ctx->q.q, true,
+                                 false, true).total;
+  if (t > 160 * 1024) return false;
+  *smem = t;
+  return true;
+}
+
 static FqLaunch fq_launcher(int nsc) { return nsc == 0 ? fq_launch_n0() : (nsc == 2 ? fq_launch_n2() : fq_launch_n4()); }
 
 // Reserve's NodeNUMAResource / DeviceShare allocations ahead of the commit (reserve_pre_kernel): on for
@@ -3698,8 +3713,10 @@ static int commit_attr_set(ks_ctx* ctx) {
   hipError_t e = pass_launcher(kernel_feat(ctx), ctx->nsc).commit_attr(qcache, smem);
   if (e != hipSuccess) KS_FAIL(ctx, KS_EHIP, "hipFuncSetAttribute(commit LDS %zu): %s", smem, hipGetErrorString(e));
   if (fq_commit(ctx, qcache, false)) {
-    e = fq_launcher(ctx->nsc).commit_attr(smem);
-    if (e != hipSuccess) KS_FAIL(ctx, KS_EHIP, "hipFuncSetAttribute(fq commit LDS %zu): %s", smem, hipGetErrorString(e));
+    size_t fsmem = smem;
+    const bool keys = fq_keys(ctx, qcache, false, &fsmem);
+    e = fq_launcher(ctx->nsc).commit_attr(keys, fsmem);
+    if (e != hipSuccess) KS_FAIL(ctx, KS_EHIP, "hipFuncSetAttribute(fq commit LDS %zu): %s", fsmem, hipGetErrorString(e));
   }
   size_t msmem = 0;
   if (mono_commit(ctx, qcache, &msmem)) {
@@ -4295,7 +4312,11 @@ static int launch_pass(ks_ctx* ctx, int32_t ppw, int sweep_blocks, const PipeSha
   rec(2, cs);
   if (ca.pre_rsv) HIPCHK(ctx, pl.reserve_pre(ctx->batch, cs, ca));  // (timed with the commit)
   if (mono) HIPCHK(ctx, pl.commit_mono(qcache, msmem, cs, ca));
-  else if (fq_commit(ctx, qcache, patch)) HIPCHK(ctx, fq_launcher(ctx->nsc).commit(smem, cs, ca));
+  else if (fq_commit(ctx, qcache, patch)) {
+    size_t fsmem = smem;
+    const bool keys = fq_keys(ctx, qcache, patch, &fsmem);
+    HIPCHK(ctx, fq_launcher(ctx->nsc).commit(keys, fsmem, cs, ca));
+  }
   else HIPCHK(ctx, pl.commit(qcache, smem, cs, ca));
   rec(2, cs);
   if (pipe) HIPCHK(ctx, hipEventRecord(ctx->pev_com[k % kPipeEvents], cs));
@@ -4487,6 +4508,11 @@ static int schedule_staged_impl(ks_ctx* ctx) {
                                          numa_cache_bytes(ctx), ctx->q.q, kernel_feat(ctx) == 0, commit_hint_variant(ctx));
     ctx->stats.commit_lds_bytes = (int64_t)L.total;
     ctx->stats.commit_helpers = L.hint ? 1 : 0;
+    size_t fsmem = 0, msmem = 0;
+    if (!mono_commit(ctx, qc, &msmem) && fq_keys(ctx, qc, pipe && pipe->patch, &fsmem)) {
+      ctx->stats.commit_lds_bytes = (int64_t)fsmem;
+      ctx->stats.commit_helpers = 2;
+    }
   }
   for (int i = 0; i < 8; ++i) ctx->stats.diag[i] = (int64_t)cnt[8 + i];
   for (size_t i = 0; i + 1 < evs.size(); i += 2) {

@@ -13,6 +13,11 @@
 //  * a monotone profile's fast pod (snapshot-best node untouched) always opens a new slot from the prefetched top
 //    row, so it skips the slot search; a slow pod's new slot can only be its second-best node or a miss;
 //  * no Reservation / NUMA / DeviceShare / dictionary state, no normalization, no cpu-bind Reserve, no ks_assume.
+//
+// KEYS = true (the slot-key table fits the LDS): a slow pod's keys on the touched slots are not evaluated
+// by wave 0 (lane = slot, one full evaluation's latency per slow pod) but ahead of time by wave 2, the evaluator:
+// whenever a slot row changes, it evaluates that one row for every pod of the pass (lane = pod) into
+// skey[slot][pod].  Wave 0's slow path is then a wait for the evaluator, one LDS read and the wave max.
 #pragma once
 
 #include "ks_pass.h"
@@ -46,13 +51,13 @@ __device__ __forceinline__ uint64_t fq_rescan(const DevNodes* dnp, const Cfg& cf
   return wave_max_u64(skip ? 0ull : gkey(o.total, node));
 }
 
-template <int NSC>
+template <int NSC, bool KEYS>
 __global__ __launch_bounds__(commit_threads(0)) void commit_fq_kernel(CommitArgs a) {
   constexpr int NT = commit_threads(0);
   extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
   const int32_t K = a.k;
   const CommitLayout lay = commit_layout(K, a.nchunks, true, (size_t)a.rsv_bytes, (size_t)a.dev_bytes, (size_t)a.numa_bytes,
-                                         a.q.q, true, false);
+                                         a.q.q, true, false, KEYS);
   SlotRow* rows = reinterpret_cast<SlotRow*>(smem_raw + lay.rows);
   PodRec* spods = reinterpret_cast<PodRec*>(smem_raw + lay.pods);
   ks_result* sres = reinterpret_cast<ks_result*>(smem_raw + lay.res);
@@ -66,9 +71,15 @@ __global__ __launch_bounds__(commit_threads(0)) void commit_fq_kernel(CommitArgs
   QuotaRowsLds qview = quota_lds(smem_raw + lay.quota, a.q.q);
   QuotaRowsLds* qlds = &qview;
   unsigned long long* touched = reinterpret_cast<unsigned long long*>(smem_raw + lay.touched);
-  int2* hdesc = reinterpret_cast<int2*>(smem_raw + lay.help);  // [issue order] {node, slot | pod << 8 | second << 16}
+  // [issue order] {node, slot | pod << 8 | second << 16 | built << 17}: one descriptor per row change.  Wave 1 builds
+  // the row of every descriptor without `built`; with KEYS wave 2 evaluates the row of every descriptor (`built`: the
+  // row is wave 0's own work, a miss's new row or a Reserve onto a touched slot, finished before the descriptor is
+  // issued; without KEYS no such descriptor is issued).  A pod issues at most one, so kMaxBatch entries suffice.
+  int2* hdesc = reinterpret_cast<int2*>(smem_raw + lay.help);
   int32_t* hpend = reinterpret_cast<int32_t*>(smem_raw + lay.help + (size_t)kMaxBatch * 8);  // descriptors issued
   int32_t* hdone = hpend + 1;                                                                // wave 0 is done
+  int32_t* heval = hpend + 2;                                                                // descriptors evaluated
+  uint32_t* skey = reinterpret_cast<uint32_t*>(smem_raw + lay.skey);  // [slot][kSlotKeyStride] (KEYS)
   unsigned long long* hready = reinterpret_cast<unsigned long long*>(smem_raw + lay.help + (size_t)kMaxBatch * 8 + 16);
   const int tid = threadIdx.x;
   const int lane = tid & 63;
@@ -81,7 +92,9 @@ __global__ __launch_bounds__(commit_threads(0)) void commit_fq_kernel(CommitArgs
   const int32_t np = topo_pass_pods(a, cursor0, min(a.batch, a.total_pods - cursor0));
   if (np == 0) return;  // a topology pod at the cursor: the next topology step takes it
 #ifdef KS_COMMIT_STAMPS
-  // diagnostic build: the same stamp points as commit_kernel (tools/diag_commit.py)
+  // diagnostic build: commit_kernel's stamp points (tools/diag_commit.py), except that the admission is part of the
+  // look-ahead's slot 1 and slot 6 is the slow path's wait (KEYS: for the evaluator, else for the builder) plus the
+  // loop's exit, so slot 2 is the evaluation (KEYS: the key read) and the wave max alone
   uint64_t ph[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   uint64_t tlast = __builtin_amdgcn_s_memtime();
 #define KS_FSTAMP(i)                                   \
@@ -155,10 +168,12 @@ __global__ __launch_bounds__(commit_threads(0)) void commit_fq_kernel(CommitArgs
   if (tid == 0) {
     *hpend = 0;
     *hdone = 0;
+    *heval = 0;
     *hready = 0ull;
   }
   __syncthreads();
-  if (tid >= 128) return;  // the other waves are done; wave 0 runs the sequential loop, wave 1 builds slot rows
+  // the other waves are done; wave 0 runs the sequential loop, wave 1 builds slot rows, wave 2 evaluates them (KEYS)
+  if (tid >= (KEYS ? 192 : 128)) return;
   KS_FSTAMP(0);
   // Opaque copies of the profile words this plugin set reads: hipcc otherwise re-loads kernel-argument words inside
   // the loop (s_load + s_waitcnt lgkmcnt(0)), which would drain every LDS read in flight.  Every other Cfg word is a
@@ -239,6 +254,39 @@ __global__ __launch_bounds__(commit_threads(0)) void commit_fq_kernel(CommitArgs
     }
   };
 
+  if (KEYS && tid >= 128) {
+    // ---- wave 2: the slot-key evaluator (lane = pod).  It takes the descriptors in issue order, so when wave 0 has
+    // seen `heval` reach the number it issued, skey[s][j] is pod j's key on slot s after every pod before j.  Wave 0
+    // changes a row it did not just create (term_take) only in a slow pod's Reserve, which comes after that pod's wait
+    // for every descriptor issued so far: the evaluator never reads a row that is being changed.  Nobody reads the
+    // table once wave 0 is done, so the wave leaves as soon as it sees `hdone`. ----
+    const int32_t pl = min(lane, np - 1);
+    const PodRec pod = spods[pl];
+    int32_t next = 0;
+    for (;;) {
+      if (__builtin_amdgcn_readfirstlane(__hip_atomic_load(hdone, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP))) break;
+      const int32_t pend =
+          __builtin_amdgcn_readfirstlane(__hip_atomic_load(hpend, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP));
+      if (next >= pend) {
+        __builtin_amdgcn_s_sleep(1);
+        continue;
+      }
+      const int32_t w = __builtin_amdgcn_readfirstlane(hdesc[next].y);
+      const int32_t s = w & 0xFF, jj = (w >> 8) & 0xFF;
+      if (!((w >> 17) & 1) &&
+          !((readlane64(__hip_atomic_load(hready, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP), 0) >> s) & 1ull)) {
+        __builtin_amdgcn_s_sleep(1);  // wave 1 is still building the row
+        continue;
+      }
+      NodeReg<NSC> r;
+      slot_to_reg<NSC>(rows[s], r);  // wave-uniform address: LDS broadcast reads
+      const EvalOut o = eval_pod_node<NSC, false>(cfg, pod, r);
+      if (lane > jj && lane < np) skey[s * kSlotKeyStride + lane] = o.reasons == 0 ? (uint32_t)(o.total + 1) : 0u;
+      ++next;
+      if (lane == 0) __hip_atomic_store(heval, next, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
+    }
+    return;
+  }
   if (tid >= 64) {
     // ---- wave 1: the slot-row builder (runs until wave 0 is done and every descriptor is built) ----
     int32_t next = 0;
@@ -248,6 +296,10 @@ __global__ __launch_bounds__(commit_threads(0)) void commit_fq_kernel(CommitArgs
       if (next < pend) {
         const int2 d = hdesc[next];
         const int32_t w = __builtin_amdgcn_readfirstlane(d.y);
+        if (KEYS && ((w >> 17) & 1)) {  // wave 0 built or changed this row itself: the evaluator's descriptor only
+          ++next;
+          continue;
+        }
         const int32_t s = w & 0xFF, jj = (w >> 8) & 0xFF;
         const int64_t* src = (((w >> 16) & 1) ? rawrun : rawtop) + jj * 32;
         const uint32_t pflags = __builtin_amdgcn_readfirstlane(spods[jj].flags);
@@ -264,7 +316,7 @@ __global__ __launch_bounds__(commit_threads(0)) void commit_fq_kernel(CommitArgs
     }
     return;
   }
-  int32_t hn = 0;     // descriptors issued to wave 1
+  int32_t hn = 0;     // descriptors issued
   uint64_t hown = 0;  // slots whose rows wave 0 built itself
   // wave 0: every row of `need` is built (wave 1's ready mask or its own)
   auto wait_rows = [&](uint64_t need) {
@@ -275,6 +327,19 @@ __global__ __launch_bounds__(commit_threads(0)) void commit_fq_kernel(CommitArgs
       if ((r & need) == need) break;
       __builtin_amdgcn_s_sleep(1);
     }
+  };
+  // wave 0 (KEYS): the evaluator has taken every descriptor issued so far
+  auto wait_keys = [&]() {
+    while (__builtin_amdgcn_readfirstlane(__hip_atomic_load(heval, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP)) < hn)
+      __builtin_amdgcn_s_sleep(1);
+  };
+  // wave 0 (KEYS): the descriptor of a row it built or changed itself (the row's LDS writes come first: release)
+  auto issue_built = [&](int32_t node, int32_t s, int32_t j) {
+    if (lane == 0) {
+      hdesc[hn] = make_int2(node, s | (j << 8) | (1 << 17));
+      __hip_atomic_store(hpend, hn + 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
+    }
+    ++hn;
   };
 
   int32_t snode = -1;  // lane s: node of slot s
@@ -332,7 +397,6 @@ __global__ __launch_bounds__(commit_threads(0)) void commit_fq_kernel(CommitArgs
                               qlds->npused, true, qr, 0u, pmask, req, /*skip_leaf=*/true);
       }
     }
-    KS_FSTAMP(6);  // (diagnostic builds: the admission part of the look-ahead)
     if (st_next) return;
     if (top && !((tw >> (tn & 63)) & 1ull)) {
       cn.fast = true;  // its row is in rawtop[j]
@@ -372,22 +436,35 @@ __global__ __launch_bounds__(commit_threads(0)) void commit_fq_kernel(CommitArgs
         }
         ++hn;
       } else {
-        // pod j: LDS broadcast into VGPRs; flags scalar so the plugin branches stay wave-uniform
-        PodRec pod = spods[j];
-        pod.flags = pflags;
         // ---- every touched node exactly (lane = slot), untouched from the candidates ----
         uint64_t key_mod = 0;
-        wait_rows(nslots >= 64 ? ~0ull : ((1ull << nslots) - 1));
-        if (lane < nslots) {
-          NodeReg<NSC> r;
-          slot_to_reg<NSC>(rows[lane], r);
-          const EvalOut o = eval_pod_node<NSC, false>(cfg, pod, r);
-          if (o.reasons == 0) key_mod = gkey(o.total, snode);
+        if (KEYS) {
+          wait_keys();
+          KS_FSTAMP(6);  // (diagnostic builds: the slow path's wait, here for the evaluator)
+          if (lane < nslots) {
+            const uint32_t v = skey[lane * kSlotKeyStride + j];
+            if (v) key_mod = ((uint64_t)v << 32) | (uint64_t)(0xFFFFFFFFu - (uint32_t)snode);  // gkey(v - 1, snode)
+          }
+        } else {
+          wait_rows(nslots >= 64 ? ~0ull : ((1ull << nslots) - 1));
+          KS_FSTAMP(6);  // (diagnostic builds: the slow path's wait, here for the builder)
+          if (lane < nslots) {
+            // pod j: LDS broadcast into VGPRs; flags scalar so the plugin branches stay wave-uniform
+            PodRec pod = spods[j];
+            pod.flags = pflags;
+            NodeReg<NSC> r;
+            slot_to_reg<NSC>(rows[lane], r);
+            const EvalOut o = eval_pod_node<NSC, false>(cfg, pod, r);
+            if (o.reasons == 0) key_mod = gkey(o.total, snode);
+          }
         }
         best = umax64(cj.umax, wave_max_u64(key_mod));
         KS_FSTAMP(2);
         uint64_t need = __ballot(!cj.exact && cj.valid && cj.ub > best);
         while (need) {
+          // (rescans are rare: the pod's record is read here)
+          PodRec pod = spods[j];
+          pod.flags = pflags;
           const uint64_t kmax = wave_max_u64(((need >> lane) & 1ull) ? cj.ub : 0ull);
           const int sel = __ffsll((long long)__ballot(((need >> lane) & 1ull) && cj.ub == kmax)) - 1;
           const int64_t c = (int64_t)(uint32_t)__shfl((int)cj.chunk, sel, 64);
@@ -427,6 +504,7 @@ __global__ __launch_bounds__(commit_threads(0)) void commit_fq_kernel(CommitArgs
             if (lane < RF_N) raw[lane] = load_field(my_col, my_w, node);
             hown |= 1ull << s;
             build_row(&rows[s], raw, podw, pflags);
+            if (KEYS) issue_built(node, s, j);
           }
         } else {
           wait_rows(1ull << s);
@@ -437,6 +515,7 @@ __global__ __launch_bounds__(commit_threads(0)) void commit_fq_kernel(CommitArgs
           } else if (lane == kLaneCounts) {
             row->pod_count += 1;
           }
+          if (KEYS) issue_built(node, s, j);
         }
       }
       KS_FSTAMP(4);
@@ -514,9 +593,10 @@ __global__ __launch_bounds__(commit_threads(0)) void commit_fq_kernel(CommitArgs
 
 // host launch wrappers of the three scalar-slot variants (ks_variant.hip, KS_FEAT == 0)
 struct FqLaunch {
-  hipError_t (*commit)(size_t smem, hipStream_t s, const CommitArgs& a);
-  hipError_t (*commit_attr)(size_t smem);
+  hipError_t (*commit)(bool keys, size_t smem, hipStream_t s, const CommitArgs& a);
+  hipError_t (*commit_attr)(bool keys, size_t smem);
 };
+// (keys: the variant with the slot-key table and the evaluator wave; smem includes the table then)
 FqLaunch fq_launch_n0();
 FqLaunch fq_launch_n2();
 FqLaunch fq_launch_n4();

@@ -472,17 +472,24 @@ static_assert(sizeof(DevHints) == 24 && sizeof(DevVar) == 16, "help region");
 
 struct CommitLayout {
   size_t rows, pods, res, raw, rawtop, rawrun, pqreq, cand_t, cand_chunk, scls, snuma, srcnt, srec, sdev, snp, quota, help,
-      touched, total;
+      touched, skey, total;
   bool hint;  // the helper waves' region is in the layout (the commit kernel runs them)
 };
 
 __host__ __device__ inline size_t align16(size_t x) { return (x + 15) / 16 * 16; }
 
+// commit_fq_kernel's slot-key table (ks_fq.h): skey[slot][pod] = the pod's score on the slot's row + 1 (0 = infeasible),
+// written by the evaluator wave with lane = pod and read by wave 0 with lane = slot.  A row stride of 65 words puts
+// both accesses on 64 different banks (a 64-word stride would make the lane = slot read a 64-way conflict).
+constexpr int kSlotKeyStride = kMaxBatch + 1;
+constexpr size_t kSlotKeyBytes = (size_t)kMaxBatch * kSlotKeyStride * 4;
+
 // hint_ok: the variant runs the helper waves (NUMA policies + DeviceShare compiled in, (FEAT & 12) == 12)
+// slot_keys: the slot-key table is in the layout (set by commit_fq_kernel's evaluator-wave variant only)
 __host__ __device__ inline CommitLayout commit_layout(int32_t k, int64_t nchunks, bool qc, size_t rsv_bytes = 0,
                                                       size_t dev_bytes = 0, size_t numa_bytes = 0,
                                                       int32_t qrows = kQuotaLdsRows, bool run = false,
-                                                      bool hint_ok = false) {
+                                                      bool hint_ok = false, bool slot_keys = false) {
   CommitLayout L;
   size_t o = 0;
   L.rows = o;
@@ -526,6 +533,8 @@ __host__ __device__ inline CommitLayout commit_layout(int32_t k, int64_t nchunks
   o += L.hint ? kHelpHintBytes : kHelpBytes;
   L.touched = o;
   o += (size_t)nchunks * 8;  // u64 per chunk: lanes touched in this pass
+  L.skey = o;
+  if (slot_keys) o += kSlotKeyBytes;
   L.total = o;
   return L;
 }

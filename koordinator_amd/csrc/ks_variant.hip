@@ -48,13 +48,15 @@ hipError_t commit_mono_attr(bool qc, size_t smem) {
 }
 
 // the monotone Fit + LoadAware + ElasticQuota commit with the quota tables in LDS (ks_fq.h)
-hipError_t commit_fq(size_t smem, hipStream_t s, const CommitArgs& a) {
-  hipLaunchKernelGGL((commit_fq_kernel<NSC>), dim3(1), dim3(commit_threads(0)), smem, s, a);
+hipError_t commit_fq(bool keys, size_t smem, hipStream_t s, const CommitArgs& a) {
+  if (keys) hipLaunchKernelGGL((commit_fq_kernel<NSC, true>), dim3(1), dim3(commit_threads(0)), smem, s, a);
+  else hipLaunchKernelGGL((commit_fq_kernel<NSC, false>), dim3(1), dim3(commit_threads(0)), smem, s, a);
   return hipGetLastError();
 }
 
-hipError_t commit_fq_attr(size_t smem) {
-  return hipFuncSetAttribute((const void*)commit_fq_kernel<NSC>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
+hipError_t commit_fq_attr(bool keys, size_t smem) {
+  const void* fn = keys ? (const void*)commit_fq_kernel<NSC, true> : (const void*)commit_fq_kernel<NSC, false>;
+  return hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
 }
 #endif
 

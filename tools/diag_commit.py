@@ -46,6 +46,14 @@ if CAT:
         print(f"{nm:20s} {cyc:14d} cycles" + (f"  n={cnt:8d}  {cyc/max(cnt,1):9.1f} cyc/pod" if cnt is not None else ""))
     sys.exit(0)
 names = ["prefetch", "lookahead(quota+cands)", "slot_eval", "rescans+cut", "reserve_row", "reserve_rest", "loop_exit"]
+if which == "c2" and os.environ.get("KS_COMMIT_FQ", "1") != "0":
+    # commit_fq_kernel (ks_fq.h) stamps the slot evaluation in two parts: the slow path's wait (for the evaluator wave's
+    # keys; with KS_FQ_KEYS=0 for the builder wave's rows) together with the few cycles of the loop's exit, then the
+    # read of the keys (KS_FQ_KEYS=0: eval_pod_node over the touched slots) and the wave max.  Its admission is part of
+    # the look-ahead's stamp.
+    names[1] = "lookahead(+admission)"
+    names[2] = "slot_eval read+max" if st["commit_helpers"] == 2 else "slot_eval in-wave"
+    names[6] = "slot_eval wait(+exit)"
 tot = sum(st["diag"][:7])
 print(w.name, {k: st[k] for k in ("passes", "cut_passes", "rescans", "slot_misses", "sweep_ms", "select_ms", "commit_ms", "total_ms")}, "fast_picks", st["diag"][7])
 for n, v in zip(names, st["diag"][:7]):
