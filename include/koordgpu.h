@@ -66,7 +66,7 @@ extern "C" {
 #define KS_DEV_WORDS (3 * KS_MAX_GPUS + KS_MAX_RDMA)
 #define KS_MAX_CPUS 256   /* logical CPUs per node topology (ks_cpu_topology); CPU ids 0..ncpus-1 */
 #define KS_CPU_WORDS 4    /* uint64 words of a CPU set (bit c = CPU c) */
-#define KS_MAX_NUMA 8     /* NUMA nodes per node (ks_numa_node_cols); the device evaluates up to 4 */
+#define KS_MAX_NUMA 8     /* NUMA nodes per node (ks_numa_node_cols); the device evaluates all 8 */
 
 /* ---- status codes ---- */
 #define KS_OK 0

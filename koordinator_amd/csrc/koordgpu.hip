@@ -764,11 +764,15 @@ __global__ __launch_bounds__(1024) void rsv_normalize_debug_kernel(int64_t n, co
 // allocation (NodeAllocation.addPodAllocation, node_allocation.go:75-100: allocated, exclusive policy).
 constexpr int kCpusetStage = 1024;
 
+// NW: the context's NUMA width (ks_numa.h); split holds 8 bits per NUMA node, a u32 per pod at width 4, a u64 at 8
+template <int NW>
 __global__ __launch_bounds__(256) void cpuset_kernel(DevCpu cpu, const int2* list, const int32_t* count_p,
-                                                     const uint32_t* split, const PodRec* pods, CpuSet* out,
+                                                     const uint32_t* split_w, const PodRec* pods, CpuSet* out,
                                                      const uint32_t* numa_flags, uint32_t* cores, int32_t default_most,
                                                      int32_t* numa_free, int64_t numa_npad, int64_t n) {
   __shared__ int2 stage[kCpusetStage];
+  using SplitT = std::conditional_t<NW == kNumaWide, uint64_t, uint32_t>;
+  const SplitT* split = reinterpret_cast<const SplitT*>(split_w);
   const int64_t node = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   const int32_t count = *count_p;
   uint64_t keys[KS_MAX_CPUS];
@@ -804,9 +808,9 @@ __global__ __launch_bounds__(256) void cpuset_kernel(DevCpu cpu, const int2* lis
       const bool most = (nf & KS_NUMA_ALLOC_MOST) ? true : ((nf & KS_NUMA_ALLOC_LEAST) ? false : default_most != 0);
       // allocateCPUSet (resource_manager.go:314-401): with a NUMA allocation one takeCPUs per allocated NUMA node over
       // its available CPUs, each against the allocation before this pod; else one over the whole node
-      const uint32_t sp = split[pod];
+      const SplitT sp = split[pod];
       CpuSet res = cs_zero();
-      for (int k = 0; k < (sp ? kNumaDev : 1); ++k) {
+      for (int k = 0; k < (sp ? NW : 1); ++k) {
         const int32_t need = sp ? (int32_t)((sp >> (8 * k)) & 0xFFu) : (int32_t)(cb >> 8);
         if (sp && need == 0) continue;
         CpuAcc a;
@@ -833,7 +837,7 @@ __global__ __launch_bounds__(256) void cpuset_kernel(DevCpu cpu, const int2* lis
     cores[node] = cores_word(t, av, (numa_flags[node] >> KS_NUMA_CPU_BIND_SHIFT) & 3u);
     // the NUMA nodes' words too: the commit kept their CPU counts, the core counts follow the CPU ids chosen here
     if (numa_free)
-      for (int k = 0; k < kNumaDev; ++k) numa_free[(int64_t)k * numa_npad + node] = numa_free_word(t, av, k);
+      for (int k = 0; k < NW; ++k) numa_free[(int64_t)k * numa_npad + node] = numa_free_word(t, av, k);
   }
 }
 
@@ -857,11 +861,12 @@ __global__ void cores_kernel(DevCpu cpu, int32_t loaded, const uint32_t* numa_fl
 // CPUs of each NUMA node available to cpuset pods (topology CPUs of the node - allocated - reserved) and its core
 // counts (numa_free_word), for the NUMA policy path's allocateCPUSet check and a required CPU bind policy's trim;
 // NUMA node k = the topology's k-th NUMA id (ids are 0..n-1, ks_load_cpu_state).
+template <int NW>
 __global__ void numa_free_kernel(DevCpu cpu, DevNuma nv, int64_t n) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   const int32_t tid = cpu.topo_id[i];
-  for (int k = 0; k < kNumaDev; ++k) {
+  for (int k = 0; k < NW; ++k) {
     int32_t f = 0;
     if (tid >= 0) {
       const CpuTopo& t = cpu.topo[tid];
@@ -1005,7 +1010,7 @@ struct ks_ctx {
   PodStage st{};   // staged pods of ks_stage_pods / ks_schedule
   PodStage est{};  // single-pod evaluation (ks_eval_pod)
   PodStage ast{};  // per-pod framework mode (ks_assume / ks_unreserve)
-  int64_t* numa_alloc = nullptr;  // [cpuset_cap][2][kNumaDev] NUMA-policy allocation per pod of the last call
+  int64_t* numa_alloc = nullptr;  // [cpuset_cap][2][numa_w] NUMA-policy allocation per pod of the last call
   void* evbuf = nullptr;          // ks_eval_pod scratch, kept across calls
   size_t evbuf_bytes = 0;
   void* ures = nullptr;           // ks_unreserve scratch: node index, the pod's cpuset and NUMA allocation
@@ -1018,7 +1023,7 @@ struct ks_ctx {
   uint64_t* cand_bound = nullptr;
   uint64_t* cand_top = nullptr;
   uint64_t* cand_second = nullptr;
-  PreRsv* pre_rsv = nullptr;       // [kMaxBatch][kPreRsvM] reserve_pre_kernel's records (NUMA / device variants)
+  void* pre_rsv = nullptr;         // [kMaxBatch][kPreRsvM] reserve_pre_kernel's records (NUMA / device variants)
   int32_t* cand_total = nullptr;
   // node sharding: shard s = rank * vshards + v owns chunks [s*nchunks/S, (s+1)*nchunks/S)
   int32_t nranks = 1, rank = 0, vshards = 1;
@@ -1080,6 +1085,9 @@ struct ks_ctx {
   // NUMA topology policies (ks_numa.h)
   void* numa_blob = nullptr;
   DevNuma nv{};
+  int32_t k_cfg = 32;        // the configured candidates per pod (k: what the commit layout leaves of it, commit_attr_set)
+  int numa_w = kNumaDev;     // NUMA width of the table and of the kernels (ks_numa.h): kNumaWide once a policy node has
+                             // more than kNumaDev NUMA nodes (numa_install)
   DevNuma* dnv = nullptr;    // device copy (always allocated: kernels take its address)
   char* numa_ckpt = nullptr;       // checkpoint copy of the mutable NUMA block (numa_mut_bytes)
   int64_t numa_policy_nodes = 0;  // nodes with a NUMA topology policy
@@ -1103,7 +1111,7 @@ struct ks_ctx {
   std::vector<int32_t> h_rsv_node; // CSR position -> node
   void* dscratch = nullptr;        // delta uploads (ks_update_*): indices + row words
   size_t dscratch_bytes = 0;
-  uint32_t* cpuset_split = nullptr;  // [cpuset_cap] per pod (CommitArgs.cpuset_split)
+  uint32_t* cpuset_split = nullptr;  // [cpuset_cap] per pod (CommitArgs.cpuset_split; 8 bytes per pod reserved)
   // pipelined passes: sweep + select on sstream while the commit runs on stream
   hipStream_t sstream = nullptr;   // shared by the process's contexts on this device (ensure_pipe), never destroyed
   hipStream_t cstream = nullptr;   // the pipelined commits: the CU the sweep stream leaves out (or `stream`)
@@ -1382,7 +1390,7 @@ int ks_create(const ks_config* cfg, ks_ctx** out) {
   ctx->cfg = *cfg;
   ctx->device = cfg->device;
   ctx->batch = cfg->batch_pods > 0 ? std::min(cfg->batch_pods, kMaxBatch) : 64;
-  ctx->k = cfg->candidates > 0 ? std::min(cfg->candidates, kMaxCand) : 32;
+  ctx->k = ctx->k_cfg = cfg->candidates > 0 ? std::min(cfg->candidates, kMaxCand) : 32;
   ctx->commit_fq = env_i64("KS_COMMIT_FQ", 1, 0, 1) != 0;  // (per context: a process can build one of each, tests / A-B)
   ctx->fq_keys = env_i64("KS_FQ_KEYS", 1, 0, 1) != 0;
   if (hipSetDevice(ctx->device) != hipSuccess || hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking) != hipSuccess) {
@@ -1403,8 +1411,8 @@ int ks_create(const ks_config* cfg, ks_ctx** out) {
   ctx->cand_top = (uint64_t*)p;
   if (dev_alloc(ctx, &p, 2 * kMaxBatch * 8) != KS_OK) goto fail;
   ctx->cand_second = (uint64_t*)p;
-  if (dev_alloc(ctx, &p, (size_t)kMaxBatch * kPreRsvM * sizeof(PreRsv)) != KS_OK) goto fail;
-  ctx->pre_rsv = (PreRsv*)p;
+  if (dev_alloc(ctx, &p, (size_t)kMaxBatch * kPreRsvM * sizeof(PreRsvT<kNumaWide>)) != KS_OK) goto fail;
+  ctx->pre_rsv = p;
   if (dev_alloc(ctx, &p, 2 * kMaxBatch * 4) != KS_OK) goto fail;
   ctx->cand_total = (int32_t*)p;
   if (dev_alloc(ctx, &p, 2 * kMaxBatch * 4) != KS_OK) goto fail;
@@ -1937,6 +1945,11 @@ static int dev_apply_held(ks_ctx* ctx) {
   HIPCHK(ctx, hipGetLastError());
   HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
   dev_free(p);
+  // the plugin set with reservations holding devices (FEAT 31) is not built at NUMA width 8 (csrc/Makefile WFEATS):
+  // refused here, at the load that completes the combination, not at the first schedule
+  if (ctx->numa_w == kNumaWide && ctx->kc.rsv && ctx->kc.dev && ctx->dev_held_any)
+    KS_FAIL(ctx, KS_EUNSUPPORTED,
+            "reservations holding devices together with a NUMA-policy node with more than %d NUMA nodes", kNumaDev);
   return KS_OK;
 }
 
@@ -2110,7 +2123,7 @@ static int rsv_install(ks_ctx* ctx, const ks_reservation_cols* rc, int32_t nr, c
   if (rsv_launch_base(ctx, nullptr, ctx->n, +1, 1) != KS_OK) return KS_EHIP;
   ctx->rsv_based = true;
   ctx->h_dev_held = held;
-  if (dev_apply_held(ctx) != KS_OK) return KS_EHIP;
+  if (int rc = dev_apply_held(ctx); rc != KS_OK) return rc;
   HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
   return KS_OK;
 }
@@ -2229,7 +2242,7 @@ static int dev_install(ks_ctx* ctx, const ks_device_cols* dc) {
   HIPCHK(ctx, hipMemcpyAsync(ctx->ddv, &ctx->dv, sizeof(DevDev), hipMemcpyHostToDevice, ctx->stream));
   ctx->dev_loaded = dc != nullptr;
   HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-  if (dev_apply_held(ctx) != KS_OK) return KS_EHIP;
+  if (int rc = dev_apply_held(ctx); rc != KS_OK) return rc;
   return check_dev_numa(ctx);
 }
 
@@ -2465,7 +2478,7 @@ static int numa_refresh_free(ks_ctx* ctx) {
   if (!ctx->numa_blob) return KS_OK;
   const size_t np = (size_t)ctx->npad;
   if (!ctx->cpu_loaded) {
-    HIPCHK(ctx, hipMemsetAsync(ctx->nv.free, 0, (size_t)kNumaDev * np * 4, ctx->stream));
+    HIPCHK(ctx, hipMemsetAsync(ctx->nv.free, 0, (size_t)ctx->numa_w * np * 4, ctx->stream));
     return KS_OK;
   }
   // the per-NUMA cpuset takes index the topology's NUMA nodes by NUMA id, and a cpu-bind pod admitted with a nil
@@ -2476,13 +2489,15 @@ static int numa_refresh_free(ks_ctx* ctx) {
       KS_FAIL(ctx, KS_EUNSUPPORTED, "node %lld: NUMA-policy node whose CPU topology NUMA ids are not 0..m-1 with m <= %d",
               (long long)i, k);
   }
-  if (ctx->n > 0)
-    hipLaunchKernelGGL(numa_free_kernel, dim3((unsigned)((ctx->n + 255) / 256)), dim3(256), 0, ctx->stream, ctx->cpu, ctx->nv,
-                       ctx->n);
+  if (ctx->n > 0) {
+    const dim3 grid((unsigned)((ctx->n + 255) / 256));
+    if (ctx->numa_w == kNumaWide) hipLaunchKernelGGL(numa_free_kernel<kNumaWide>, grid, dim3(256), 0, ctx->stream, ctx->cpu, ctx->nv, ctx->n);
+    else hipLaunchKernelGGL(numa_free_kernel<kNumaDev>, grid, dim3(256), 0, ctx->stream, ctx->cpu, ctx->nv, ctx->n);
+  }
   HIPCHK(ctx, hipGetLastError());
   // a load re-bases the checkpoint (as the CPU state's own checkpoint is re-based by ks_load_cpu_state)
   char* ck_free = ctx->numa_ckpt + ((char*)ctx->nv.free - (char*)ctx->nv.used);
-  HIPCHK(ctx, hipMemcpyAsync(ck_free, ctx->nv.free, (size_t)kNumaDev * np * 4, hipMemcpyDeviceToDevice, ctx->stream));
+  HIPCHK(ctx, hipMemcpyAsync(ck_free, ctx->nv.free, (size_t)ctx->numa_w * np * 4, hipMemcpyDeviceToDevice, ctx->stream));
   return KS_OK;
 }
 
@@ -2506,8 +2521,7 @@ static int check_dev_numa(ks_ctx* ctx) {
 // NUMA node resources of the policy nodes; nc == nullptr installs an empty table (every policy node
 // then reports "missing NUMA resources", as the reference does without a NodeResourceTopology).
 // Layout: count | total | mutable {used, off, cs, free, present} | checkpoint copy of the mutable block.
-static size_t numa_mut_bytes(size_t np) {
-  constexpr int K = kNumaDev;
+static size_t numa_mut_bytes(size_t np, int K) {
   return 2 * K * np * 8 + K * np * 8 + 2 * K * np * 4 + align16(np * 4);
 }
 
@@ -2516,18 +2530,21 @@ static size_t numa_mut_bytes(size_t np) {
 struct NumaRow {
   int32_t cnt = 0;
   uint32_t pres = 0;
-  int64_t tot[2 * kNumaDev] = {}, used[2 * kNumaDev] = {}, off[kNumaDev] = {};
-  int32_t cs[kNumaDev] = {};
+  int64_t tot[2 * kNumaWide] = {}, used[2 * kNumaWide] = {}, off[kNumaWide] = {};  // [q * K + k] at width K
+  int32_t cs[kNumaWide] = {};
 };
+// K: the table's NUMA width; a policy node with more NUMA nodes than K is refused (reload: a load picks the width)
 static int numa_encode(ks_ctx* ctx, const ks_numa_node_cols* nc, int64_t r, int64_t node, uint32_t f, double ratio,
-                       NumaRow& w) {
-  constexpr int K = kNumaDev;
+                       int K, NumaRow& w) {
   w = NumaRow{};
   const uint32_t pol = (f >> KS_NUMA_POLICY_SHIFT) & 3u;
   const int32_t c = nc->count[r];
   if (c < 0 || c > KS_MAX_NUMA) KS_FAIL(ctx, KS_EINVAL, "node %lld: NUMA node count %d", (long long)node, c);
   if (pol == 0) return KS_OK;
-  if (c > K) KS_FAIL(ctx, KS_EUNSUPPORTED, "node %lld: %d NUMA nodes with a NUMA policy (the device evaluates up to %d)", (long long)node, c, K);
+  if (c > K)
+    KS_FAIL(ctx, KS_EUNSUPPORTED,
+            "node %lld: %d NUMA nodes with a NUMA policy on a NUMA table loaded at width %d: reload the table with "
+            "ks_load_numa_nodes (a load picks width %d)", (long long)node, c, K, kNumaWide);
   w.cnt = c;
   for (int k = 0; k < c; ++k) {
     const size_t o = (size_t)r * KS_MAX_NUMA + k;
@@ -2553,10 +2570,16 @@ static int numa_encode(ks_ctx* ctx, const ks_numa_node_cols* nc, int64_t r, int6
 
 static int numa_install(ks_ctx* ctx, const ks_numa_node_cols* nc, const uint32_t* flags_h, const double* ratio_h) {
   const size_t np = (size_t)ctx->npad;
-  constexpr int K = kNumaDev;
+  // the width: 8 once a policy node has more than 4 NUMA nodes (the 4-wide kernels are the faster ones)
+  int K = kNumaDev;
+  for (int64_t i = 0; nc && i < ctx->n; ++i)
+    if (((flags_h[i] >> KS_NUMA_POLICY_SHIFT) & 3u) != 0 && nc->count[i] > kNumaDev && nc->count[i] <= KS_MAX_NUMA) K = kNumaWide;
+  if (K == kNumaWide && ctx->kc.rsv && ctx->kc.dev && ctx->dev_held_any)  // (FEAT 31 is built at width 4 only)
+    KS_FAIL(ctx, KS_EUNSUPPORTED,
+            "reservations holding devices together with a NUMA-policy node with more than %d NUMA nodes", kNumaDev);
   const size_t o_cnt = 0, o_tot = align16(np * 4), o_used = o_tot + 2 * K * np * 8, o_off = o_used + 2 * K * np * 8,
                o_cs = o_off + K * np * 8, o_free = o_cs + K * np * 4, o_pres = o_free + K * np * 4,
-               o_ck = o_pres + align16(np * 4), bytes = o_ck + numa_mut_bytes(np);
+               o_ck = o_pres + align16(np * 4), bytes = o_ck + numa_mut_bytes(np, K);
   std::vector<char> h(bytes, 0);
   int32_t* cnt = (int32_t*)(h.data() + o_cnt);
   int64_t* tot = (int64_t*)(h.data() + o_tot);
@@ -2567,7 +2590,7 @@ static int numa_install(ks_ctx* ctx, const ks_numa_node_cols* nc, const uint32_t
   ctx->h_numa_k.assign((size_t)ctx->n, 0);
   for (int64_t i = 0; nc && i < ctx->n; ++i) {
     NumaRow w;
-    if (int rc = numa_encode(ctx, nc, i, i, flags_h[i], ratio_h ? ratio_h[i] : 0.0, w); rc != KS_OK) return rc;
+    if (int rc = numa_encode(ctx, nc, i, i, flags_h[i], ratio_h ? ratio_h[i] : 0.0, K, w); rc != KS_OK) return rc;
     cnt[i] = w.cnt;
     ctx->h_numa_k[(size_t)i] = (int8_t)w.cnt;
     pres[i] = w.pres;
@@ -2582,6 +2605,7 @@ static int numa_install(ks_ctx* ctx, const ks_numa_node_cols* nc, const uint32_t
   }
   dev_free(ctx->numa_blob);
   if (dev_alloc(ctx, &ctx->numa_blob, bytes) != KS_OK) return KS_ENOMEM;
+  ctx->numa_w = K;
   char* b = (char*)ctx->numa_blob;
   HIPCHK(ctx, hipMemcpyAsync(b, h.data(), bytes, hipMemcpyHostToDevice, ctx->stream));
   DevNuma& v = ctx->nv;
@@ -2597,7 +2621,7 @@ static int numa_install(ks_ctx* ctx, const ks_numa_node_cols* nc, const uint32_t
   ctx->numa_ckpt = b + o_ck;
   HIPCHK(ctx, hipMemcpyAsync(ctx->dnv, &v, sizeof(DevNuma), hipMemcpyHostToDevice, ctx->stream));
   if (int rc = numa_refresh_free(ctx); rc != KS_OK) return rc;
-  HIPCHK(ctx, hipMemcpyAsync(ctx->numa_ckpt, v.used, numa_mut_bytes(np), hipMemcpyDeviceToDevice, ctx->stream));
+  HIPCHK(ctx, hipMemcpyAsync(ctx->numa_ckpt, v.used, numa_mut_bytes(np, ctx->numa_w), hipMemcpyDeviceToDevice, ctx->stream));
   HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
   return check_dev_numa(ctx);
 }
@@ -2639,14 +2663,14 @@ int ks_update_numa_nodes(ks_ctx* ctx, const int32_t* idx, const ks_numa_node_col
   HIPCHK(ctx, hipMemcpyAsync(flags.data(), ctx->d.numa_flags, n * 4, hipMemcpyDeviceToHost, ctx->stream));
   HIPCHK(ctx, hipMemcpyAsync(ratio.data(), ctx->d.numa_ratio, n * 8, hipMemcpyDeviceToHost, ctx->stream));
   HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-  constexpr int K = kNumaDev;
+  const int K = ctx->numa_w;
   std::vector<int32_t> cnt((size_t)m), cs((size_t)m * K);
   std::vector<uint32_t> pres((size_t)m);
   std::vector<int64_t> tot((size_t)m * 2 * K), used((size_t)m * 2 * K), off((size_t)m * K);
   for (int64_t i = 0; i < m; ++i) {
     const int32_t node = ix[(size_t)i];
     NumaRow w;
-    if (int rc = numa_encode(ctx, rows, i, node, flags[(size_t)node], ratio[(size_t)node], w); rc != KS_OK) return rc;
+    if (int rc = numa_encode(ctx, rows, i, node, flags[(size_t)node], ratio[(size_t)node], K, w); rc != KS_OK) return rc;
     cnt[(size_t)i] = w.cnt;
     pres[(size_t)i] = w.pres;
     // word-major [w][m] (scatter_words)
@@ -2677,7 +2701,8 @@ int ks_update_numa_nodes(ks_ctx* ctx, const int32_t* idx, const ks_numa_node_col
 int ks_read_numa_nodes(ks_ctx* ctx, int64_t* used_cpu, int64_t* used_memory) {
   if (!ctx) return KS_EINVAL;
   const size_t n = (size_t)ctx->n, np = (size_t)ctx->npad;
-  std::vector<int64_t> u(2 * kNumaDev * (np ? np : 1), 0);
+  const int W = ctx->numa_w;
+  std::vector<int64_t> u((size_t)2 * W * (np ? np : 1), 0);
   std::vector<uint32_t> pr(np ? np : 1, 0);
   if (ctx->numa_blob && n) {
     HIPCHK(ctx, hipMemcpyAsync(u.data(), ctx->nv.used, u.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
@@ -2688,7 +2713,7 @@ int ks_read_numa_nodes(ks_ctx* ctx, int64_t* used_cpu, int64_t* used_memory) {
     if (outs[r])
       for (size_t i = 0; i < n; ++i)
         for (int k = 0; k < KS_MAX_NUMA; ++k)
-          outs[r][i * KS_MAX_NUMA + k] = k < kNumaDev ? u[((size_t)r * kNumaDev + k) * np + i] : 0;
+          outs[r][i * KS_MAX_NUMA + k] = k < W ? u[((size_t)r * W + k) * np + i] : 0;
   return KS_OK;
 }
 
@@ -3495,7 +3520,7 @@ static int kernel_feat(const ks_ctx* ctx);
 // the context's commit variant runs the helper waves (NUMA policies + DeviceShare compiled in, ks_pass.h)
 static bool commit_hint_variant(const ks_ctx* ctx) { return (kernel_feat(ctx) & 12) == 12; }
 static size_t numa_cache_bytes(const ks_ctx* ctx) {
-  return ctx->kc.numa_pol ? (size_t)kMaxBatch * kNumaSlotWords * 8 : 0;
+  return ctx->kc.numa_pol ? (size_t)kMaxBatch * (6 * ctx->numa_w + 1) * 8 : 0;  // NumaSlotT<numa_w>::kWords per slot
 }
 
 // Quota rows are cached in LDS for the pass when the table is small enough and the LDS image fits.
@@ -3567,7 +3592,17 @@ static int32_t commit_rcap(const ks_ctx* ctx, bool* qcache) {
 }
 
 // the launch wrappers of the FEAT variant (ks_variant.hip)
-static PassLaunch pass_launcher(int feat, int nsc) {
+// wide: the context's NUMA width is kNumaWide (only the NUMA topology policy plugin sets have such kernels)
+static PassLaunch pass_launcher(int feat, int nsc, bool wide) {
+#define KS_PICK(F) return nsc == 0 ? pass_launch_f##F##_n0_w8() : (nsc == 2 ? pass_launch_f##F##_n2_w8() : pass_launch_f##F##_n4_w8())
+  if (wide)
+    switch (feat) {
+      case 15: KS_PICK(15);
+      case 14: KS_PICK(14);
+      case 11: KS_PICK(11);
+      default: break;
+    }
+#undef KS_PICK
 #define KS_PICK(F) return nsc == 0 ? pass_launch_f##F##_n0() : (nsc == 2 ? pass_launch_f##F##_n2() : pass_launch_f##F##_n4())
   switch (feat) {
     case 31: KS_PICK(31);
@@ -3704,13 +3739,25 @@ static bool pre_reserve(const ks_ctx* ctx) {
 
 // the commit kernel's LDS size for this context: checked against the CU's 160 KB and set on the variant
 static int commit_attr_set(ks_ctx* ctx) {
+  // (unreachable: the loads refuse the combination, dev_apply_held / numa_install)
+  if (ctx->numa_w == kNumaWide && kernel_feat(ctx) == 31)
+    KS_FAIL(ctx, KS_EUNSUPPORTED,
+            "reservations holding devices together with a NUMA-policy node with more than %d NUMA nodes", kNumaDev);
+  // A NUMA table at width 8 doubles the slots' NUMA cache (25 KB); next to DeviceShare's slot cache the layout then
+  // exceeds the LDS at the default 32 candidates per pod.  Such a context keeps fewer candidates per pod: the
+  // placements do not depend on the list length (a pod whose list runs out cuts the pass), only the pass count does.
+  ctx->k = ctx->k_cfg;
+  while (ctx->numa_w == kNumaWide && ctx->k > 8 &&
+         commit_layout(ctx->k, ctx->nchunks, false, 0, dev_cache_bytes(ctx), numa_cache_bytes(ctx), ctx->q.q,
+                       kernel_feat(ctx) == 0, commit_hint_variant(ctx)).total + 64 > 160 * 1024)
+    ctx->k -= 8;
   bool qcache = false;
   const int32_t rcap = commit_rcap(ctx, &qcache);
   const size_t smem = commit_layout(ctx->k, ctx->nchunks, qcache, rsv_cache_bytes(ctx, rcap), dev_cache_bytes(ctx),
                                     numa_cache_bytes(ctx), ctx->q.q, kernel_feat(ctx) == 0, commit_hint_variant(ctx)).total;
   if (smem > 160 * 1024)
     KS_FAIL(ctx, KS_EUNSUPPORTED, "too many nodes for the commit kernel's LDS (%lld nodes, %zu B)", (long long)ctx->n, smem);
-  hipError_t e = pass_launcher(kernel_feat(ctx), ctx->nsc).commit_attr(qcache, smem);
+  hipError_t e = pass_launcher(kernel_feat(ctx), ctx->nsc, ctx->numa_w == kNumaWide).commit_attr(qcache, smem);
   if (e != hipSuccess) KS_FAIL(ctx, KS_EHIP, "hipFuncSetAttribute(commit LDS %zu): %s", smem, hipGetErrorString(e));
   if (fq_commit(ctx, qcache, false)) {
     size_t fsmem = smem;
@@ -3720,7 +3767,7 @@ static int commit_attr_set(ks_ctx* ctx) {
   }
   size_t msmem = 0;
   if (mono_commit(ctx, qcache, &msmem)) {
-    e = pass_launcher(0, ctx->nsc).commit_mono_attr(qcache, msmem);
+    e = pass_launcher(0, ctx->nsc, false).commit_mono_attr(qcache, msmem);
     if (e != hipSuccess) KS_FAIL(ctx, KS_EHIP, "hipFuncSetAttribute(mono commit LDS %zu): %s", msmem, hipGetErrorString(e));
   }
   return KS_OK;
@@ -3734,7 +3781,7 @@ static int ensure_cpuset_bufs(ks_ctx* ctx, int32_t np) {
   ctx->cpuset_list = nullptr;
   const int32_t cap = std::max<int32_t>(np, 64);
   const size_t o_n = (size_t)cap * 8, o_out = o_n + 16, o_split = o_out + (size_t)cap * sizeof(CpuSet),
-               o_alloc = align16(o_split + (size_t)cap * 4), bytes = o_alloc + (size_t)cap * 2 * kNumaDev * 8;
+               o_alloc = align16(o_split + (size_t)cap * 8), bytes = o_alloc + (size_t)cap * 2 * kNumaWide * 8;  // (either width)
   if (dev_alloc(ctx, &p, bytes) != KS_OK) return KS_ENOMEM;
   ctx->cpuset_list = (int2*)p;
   ctx->cpuset_n = (int32_t*)((char*)p + o_n);
@@ -4020,14 +4067,24 @@ static TopoKArgs topo_args(ks_ctx* ctx, PodStage& st, const int32_t* cursor, con
   return a;
 }
 
+// cpuset_kernel at the context's NUMA width
+static void cpuset_launch(ks_ctx* ctx, const PodRec* recs) {
+  const dim3 grid((unsigned)((ctx->n + 255) / 256));
+  const int32_t most = (int32_t)(ctx->cfg.numa.numa_scoring_strategy == KS_MOST_ALLOCATED);
+  if (ctx->numa_w == kNumaWide)
+    hipLaunchKernelGGL(cpuset_kernel<kNumaWide>, grid, dim3(256), 0, ctx->stream, ctx->cpu, (const int2*)ctx->cpuset_list,
+                       (const int32_t*)ctx->cpuset_n, (const uint32_t*)ctx->cpuset_split, recs, ctx->cpuset_out,
+                       (const uint32_t*)ctx->d.numa_flags, ctx->d.cpu_cores, most, numa_words(ctx), ctx->nv.npad, ctx->n);
+  else
+    hipLaunchKernelGGL(cpuset_kernel<kNumaDev>, grid, dim3(256), 0, ctx->stream, ctx->cpu, (const int2*)ctx->cpuset_list,
+                       (const int32_t*)ctx->cpuset_n, (const uint32_t*)ctx->cpuset_split, recs, ctx->cpuset_out,
+                       (const uint32_t*)ctx->d.numa_flags, ctx->d.cpu_cores, most, numa_words(ctx), ctx->nv.npad, ctx->n);
+}
+
 // the pass's CPU ids (cores mode): exact per-node core counts for the next sweep (Cfg.cores)
 static int cores_pass_refresh(ks_ctx* ctx) {
   if (!(ctx->kc.cores && ctx->cpu_loaded)) return KS_OK;
-  hipLaunchKernelGGL(cpuset_kernel, dim3((unsigned)((ctx->n + 255) / 256)), dim3(256), 0, ctx->stream, ctx->cpu,
-                     (const int2*)ctx->cpuset_list, (const int32_t*)ctx->cpuset_n, (const uint32_t*)ctx->cpuset_split,
-                     (const PodRec*)ctx->st.recs, ctx->cpuset_out, (const uint32_t*)ctx->d.numa_flags,
-                     ctx->d.cpu_cores, (int32_t)(ctx->cfg.numa.numa_scoring_strategy == KS_MOST_ALLOCATED),
-                     numa_words(ctx), ctx->nv.npad, ctx->n);
+  cpuset_launch(ctx, (const PodRec*)ctx->st.recs);
   HIPCHK(ctx, hipMemsetAsync(ctx->cpuset_n, 0, 4, ctx->stream));
   return KS_OK;
 }
@@ -4044,7 +4101,7 @@ static int topo_step(ks_ctx* ctx) {
   HIPCHK(ctx, launch_topo_sums(ctx->stream, ta));
   HIPCHK(ctx, launch_eval_debug(ctx->nsc, (int)((n + 255) / 256), ctx->stream, ctx->d, ctx->drv, ctx->ddv, ctx->dnv,
                                 ctx->kc, ctx->st.recs, n, eb.dr, nullptr, eb.dt, eb.draw, eb.dhi, eb.ddraw, ctx->st.stat,
-                                eb.dtraw, eb.daraw, &ta, kernel_feat(ctx)));
+                                eb.dtraw, eb.daraw, &ta, kernel_feat(ctx), ctx->numa_w));
   HIPCHK(ctx, launch_topo_pts(ctx->stream, ta));
   const int feat = kernel_feat(ctx);
   if ((feat == 0 || feat == 4) && !ctx->kc.dev && !ctx->kc.rsv && !ctx->kc.numa && !ctx->cpu_loaded) {
@@ -4088,7 +4145,7 @@ static int topo_step(ks_ctx* ctx) {
   ca.cand_bound = ctx->topo_cbound;
   ca.cand_top = ctx->topo_ctop;
   ca.cand_second = ctx->topo_csecond;
-  HIPCHK(ctx, pass_launcher(kernel_feat(ctx), ctx->nsc).commit(qcache, smem, ctx->stream, ca));
+  HIPCHK(ctx, pass_launcher(kernel_feat(ctx), ctx->nsc, ctx->numa_w == kNumaWide).commit(qcache, smem, ctx->stream, ca));
   return cores_pass_refresh(ctx);
 }
 
@@ -4159,7 +4216,7 @@ static int launch_pass(ks_ctx* ctx, int32_t ppw, int sweep_blocks, const PipeSha
   sa.phase = 1;
   // One sweep launch per virtual shard (a rank's virtual shards are swept as separate chunk ranges, so the
   // c0 > 0 decode of every non-first shard runs on one GPU too); timed together as one launch.
-  const PassLaunch pl = pass_launcher(feat, NSC);
+  const PassLaunch pl = pass_launcher(feat, NSC, ctx->numa_w == kNumaWide);
   hipError_t le = hipSuccess;
   auto sweep = [&](int blocks, hipStream_t st) {
     for (int32_t v = 0; v < ctx->vshards && le == hipSuccess; ++v) {
@@ -4382,7 +4439,7 @@ static int schedule_staged_impl(ks_ctx* ctx) {
   if (ctx->cpuset_list) {
     HIPCHK(ctx, hipMemsetAsync(ctx->cpuset_n, 0, 4, ctx->stream));
     HIPCHK(ctx, hipMemsetAsync(ctx->cpuset_out, 0, (size_t)np * sizeof(CpuSet), ctx->stream));
-    HIPCHK(ctx, hipMemsetAsync(ctx->numa_alloc, 0, (size_t)np * 2 * kNumaDev * 8, ctx->stream));
+    HIPCHK(ctx, hipMemsetAsync(ctx->numa_alloc, 0, (size_t)np * 2 * ctx->numa_w * 8, ctx->stream));
   }
   HIPCHK(ctx, hipMemsetAsync(ctx->cursor, 0, 4, ctx->stream));
   HIPCHK(ctx, hipMemsetAsync(ctx->counters, 0, 256, ctx->stream));
@@ -4480,11 +4537,7 @@ static int schedule_staged_impl(ks_ctx* ctx) {
   }
   if (ctx->cpu_loaded && ctx->n > 0) {
     // the CPU ids of the pass's cpu-bind Reserves (ks_cpuset.h), per node in placement order
-    hipLaunchKernelGGL(cpuset_kernel, dim3((unsigned)((ctx->n + 255) / 256)), dim3(256), 0, ctx->stream, ctx->cpu,
-                       (const int2*)ctx->cpuset_list, (const int32_t*)ctx->cpuset_n, (const uint32_t*)ctx->cpuset_split,
-                       (const PodRec*)ctx->st.recs, ctx->cpuset_out, (const uint32_t*)ctx->d.numa_flags,
-                       ctx->d.cpu_cores, (int32_t)(ctx->cfg.numa.numa_scoring_strategy == KS_MOST_ALLOCATED),
-                       numa_words(ctx), ctx->nv.npad, ctx->n);
+    cpuset_launch(ctx, (const PodRec*)ctx->st.recs);
     HIPCHK(ctx, hipGetLastError());
   }
   HIPCHK(ctx, hipEventRecord(t1, ctx->stream));
@@ -4572,7 +4625,7 @@ int ks_checkpoint(ks_ctx* ctx) {
   if (ctx->cpu_loaded)
     HIPCHK(ctx, hipMemcpyAsync(ctx->cpu_ckpt, ctx->cpu.allocated, (size_t)3 * ctx->cpu.npad * sizeof(CpuSet), hipMemcpyDeviceToDevice, ctx->stream));
   if (ctx->numa_blob)
-    HIPCHK(ctx, hipMemcpyAsync(ctx->numa_ckpt, ctx->nv.used, numa_mut_bytes((size_t)ctx->npad), hipMemcpyDeviceToDevice, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(ctx->numa_ckpt, ctx->nv.used, numa_mut_bytes((size_t)ctx->npad, ctx->numa_w), hipMemcpyDeviceToDevice, ctx->stream));
   if (ctx->rsv_blob) {
     HIPCHK(ctx, hipMemcpyAsync(ctx->rsv_allocd_ckpt, ctx->rv.allocd, (size_t)kRsvDims * ctx->rv.nr * 8, hipMemcpyDeviceToDevice, ctx->stream));
     HIPCHK(ctx, hipMemcpyAsync(ctx->rsv_dald_ckpt, ctx->rv.dald, (size_t)kDevQW * ctx->rv.nr * 8, hipMemcpyDeviceToDevice, ctx->stream));
@@ -4596,7 +4649,7 @@ int ks_restore(ks_ctx* ctx) {
   if (ctx->cpu_loaded)
     HIPCHK(ctx, hipMemcpyAsync(ctx->cpu.allocated, ctx->cpu_ckpt, (size_t)3 * ctx->cpu.npad * sizeof(CpuSet), hipMemcpyDeviceToDevice, ctx->stream));
   if (ctx->numa_blob)
-    HIPCHK(ctx, hipMemcpyAsync(ctx->nv.used, ctx->numa_ckpt, numa_mut_bytes((size_t)ctx->npad), hipMemcpyDeviceToDevice, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(ctx->nv.used, ctx->numa_ckpt, numa_mut_bytes((size_t)ctx->npad, ctx->numa_w), hipMemcpyDeviceToDevice, ctx->stream));
   if (ctx->rsv_blob) {
     HIPCHK(ctx, hipMemcpyAsync(ctx->rv.allocd, ctx->rsv_allocd_ckpt, (size_t)kRsvDims * ctx->rv.nr * 8, hipMemcpyDeviceToDevice, ctx->stream));
     HIPCHK(ctx, hipMemcpyAsync(ctx->rv.dald, ctx->rsv_dald_ckpt, (size_t)kDevQW * ctx->rv.nr * 8, hipMemcpyDeviceToDevice, ctx->stream));
@@ -4679,7 +4732,7 @@ int ks_update_devices(ks_ctx* ctx, const int32_t* idx, const ks_device_cols* row
     return KS_EHIP;
   for (int64_t i = 0; i < m; ++i) ctx->h_dev_ids[(size_t)ix[i]] = ids[(size_t)i];
   ctx->dev_loaded = true;
-  if (dev_apply_held(ctx) != KS_OK) return KS_EHIP;
+  if (int rc = dev_apply_held(ctx); rc != KS_OK) return rc;
   return check_dev_numa(ctx);
 }
 
@@ -4826,13 +4879,13 @@ int ks_eval_pod(ks_ctx* ctx, const ks_pod_cols* pod, uint32_t* reasons, int64_t*
     HIPCHK(ctx, launch_topo_sums(ctx->stream, ta));
     HIPCHK(ctx, launch_eval_debug(ctx->nsc, blocks, ctx->stream, ctx->d, ctx->drv, ctx->ddv, ctx->dnv, ctx->kc,
                                   ctx->est.recs, n, dr, ds, dt, draw, dhi, ddraw, ctx->est.stat, dtraw, daraw, &ta,
-                                  kernel_feat(ctx)));
+                                  kernel_feat(ctx), ctx->numa_w));
     HIPCHK(ctx, launch_topo_pts(ctx->stream, ta));
     HIPCHK(ctx, launch_topo_norm(ctx->stream, ta));
   } else if (blocks > 0) {
     HIPCHK(ctx, launch_eval_debug(ctx->nsc, blocks, ctx->stream, ctx->d, ctx->drv, ctx->ddv, ctx->dnv, ctx->kc,
                                   ctx->est.recs, n, dr, ds, dt, draw, dhi, ddraw, ctx->est.stat, dtraw, daraw, nullptr,
-                                  kernel_feat(ctx)));
+                                  kernel_feat(ctx), ctx->numa_w));
     if (ctx->kc.dev)
       hipLaunchKernelGGL(dev_normalize_debug_kernel, dim3(1), dim3(1024), 0, ctx->stream, n, dr, ddraw, ds, dt,
                          ctx->cfg.deviceshare.plugin_weight);
@@ -4874,8 +4927,9 @@ struct UnreserveArgs {
   int32_t node, gi;        // node; the reservation's CSR position (-1 = none)
   uint32_t gmin, rmin;     // DeviceShare minors of the allocation
   const uint64_t* cpuset;  // [KS_CPU_WORDS] the pod's CPUs
-  const int64_t* nalloc;   // [2][kNumaDev] its NUMA-node allocation (cpu milli, memory)
+  const int64_t* nalloc;   // [2][numa_w] its NUMA-node allocation (cpu milli, memory)
   int32_t quota, dev, cpu_loaded, numa_pol, ratio_amp;
+  int32_t numa_w;          // the NUMA table's width (DevNuma)
   const TopoRec* topo;     // PodTopologySpread / InterPodAffinity: the pod's properties leave the node's counters
   const int32_t* topo_props;
   int32_t* topo_count;
@@ -4966,7 +5020,7 @@ __global__ void unreserve_kernel(UnreserveArgs a) {
       }
       if (a.numa_pol && tid >= 0 && a.nv.count[n] > 0) {
         const CpuTopo& t = a.cpu.topo[tid];
-        for (int k = 0; k < kNumaDev && k < a.nv.count[n]; ++k) {
+        for (int k = 0; k < a.numa_w && k < a.nv.count[n]; ++k) {
           const int32_t ck = cs_count(cs_and(cs, t.node_mask[k]));
           if (!ck) continue;
           const int64_t o = (int64_t)k * a.nv.npad + n;
@@ -4980,10 +5034,10 @@ __global__ void unreserve_kernel(UnreserveArgs a) {
     }
   }
   if (a.numa_pol && a.nalloc && a.nv.count[n] > 0) {
-    for (int k = 0; k < kNumaDev && k < a.nv.count[n]; ++k)
+    for (int k = 0; k < a.numa_w && k < a.nv.count[n]; ++k)
       for (int r = 0; r < 2; ++r) {
-        const int64_t o = ((int64_t)r * kNumaDev + k) * a.nv.npad + n;
-        const int64_t v = a.nv.used[o] - a.nalloc[r * kNumaDev + k];
+        const int64_t o = ((int64_t)r * a.numa_w + k) * a.nv.npad + n;
+        const int64_t v = a.nv.used[o] - a.nalloc[r * a.numa_w + k];
         a.nv.used[o] = v < 0 ? 0 : v;
       }
   }
@@ -5022,35 +5076,32 @@ int ks_assume(ks_ctx* ctx, const ks_pod_cols* pod, int32_t node, ks_result* out,
   if (ctx->cpuset_list) {
     HIPCHK(ctx, hipMemsetAsync(ctx->cpuset_n, 0, 4, ctx->stream));
     HIPCHK(ctx, hipMemsetAsync(ctx->cpuset_out, 0, sizeof(CpuSet), ctx->stream));
-    HIPCHK(ctx, hipMemsetAsync(ctx->numa_alloc, 0, 2 * kNumaDev * 8, ctx->stream));
+    HIPCHK(ctx, hipMemsetAsync(ctx->numa_alloc, 0, (size_t)2 * ctx->numa_w * 8, ctx->stream));
   }
   bool qcache = false;
   size_t smem = 0;
   CommitArgs ca = commit_args(ctx, ctx->ast, 1, 1, &qcache, &smem);
   ca.force = 1;
   if (ca.topo) ca.topo = 3;  // count the pod's properties on the node
-  HIPCHK(ctx, pass_launcher(kernel_feat(ctx), ctx->nsc).commit(qcache, smem, ctx->stream, ca));
+  HIPCHK(ctx, pass_launcher(kernel_feat(ctx), ctx->nsc, ctx->numa_w == kNumaWide).commit(qcache, smem, ctx->stream, ca));
   if (ctx->cpu_loaded && ctx->n > 0) {
-    hipLaunchKernelGGL(cpuset_kernel, dim3((unsigned)((ctx->n + 255) / 256)), dim3(256), 0, ctx->stream, ctx->cpu,
-                       (const int2*)ctx->cpuset_list, (const int32_t*)ctx->cpuset_n, (const uint32_t*)ctx->cpuset_split,
-                       (const PodRec*)ctx->ast.recs, ctx->cpuset_out, (const uint32_t*)ctx->d.numa_flags,
-                       ctx->d.cpu_cores, (int32_t)(ctx->cfg.numa.numa_scoring_strategy == KS_MOST_ALLOCATED),
-                       numa_words(ctx), ctx->nv.npad, ctx->n);
+    cpuset_launch(ctx, (const PodRec*)ctx->ast.recs);
     HIPCHK(ctx, hipGetLastError());
   }
   HIPCHK(ctx, hipMemcpyAsync(out, ctx->ast.results, sizeof(ks_result), hipMemcpyDeviceToHost, ctx->stream));
-  int64_t na[2 * kNumaDev] = {0};
+  const int W = ctx->numa_w;
+  int64_t na[2 * kNumaWide] = {0};
   if (cpuset) {
     if (ctx->cpuset_list) HIPCHK(ctx, hipMemcpyAsync(cpuset, ctx->cpuset_out, sizeof(CpuSet), hipMemcpyDeviceToHost, ctx->stream));
     else memset(cpuset, 0, sizeof(CpuSet));
   }
   if (numa_alloc && ctx->cpuset_list)
-    HIPCHK(ctx, hipMemcpyAsync(na, ctx->numa_alloc, sizeof(na), hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(na, ctx->numa_alloc, (size_t)2 * W * 8, hipMemcpyDeviceToHost, ctx->stream));
   HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
   if (numa_alloc) {
     memset(numa_alloc, 0, sizeof(int64_t) * KS_MAX_NUMA * 2);
-    for (int k = 0; k < kNumaDev; ++k)
-      for (int r = 0; r < 2; ++r) numa_alloc[k * 2 + r] = na[r * kNumaDev + k];
+    for (int k = 0; k < W; ++k)
+      for (int r = 0; r < 2; ++r) numa_alloc[k * 2 + r] = na[r * W + k];
   }
   // the assume wrote pod 0's slots of the batch's cpuset and NUMA-allocation buffers: the last ks_schedule*'s
   // CPU sets are gone, so ks_fetch_cpusets / ks_fetch_numa_alloc refuse until the next schedule
@@ -5079,7 +5130,7 @@ int ks_unreserve(ks_ctx* ctx, const ks_pod_cols* pod, const ks_result* r, const 
   }
   HIPCHK(ctx, hipSetDevice(ctx->device));
   if (ensure_stage(ctx, ctx->ast, 1) != KS_OK) return KS_ENOMEM;
-  if (!ctx->ures && dev_alloc(ctx, &ctx->ures, 16 + sizeof(CpuSet) + 2 * kNumaDev * 8) != KS_OK) return KS_ENOMEM;
+  if (!ctx->ures && dev_alloc(ctx, &ctx->ures, 16 + sizeof(CpuSet) + 2 * kNumaWide * 8) != KS_OK) return KS_ENOMEM;
   if (stage_cols(ctx, ctx->ast, pod, 1) != KS_OK || prep_stage(ctx, ctx->ast, 1) != KS_OK) return KS_EHIP;
   char* u = (char*)ctx->ures;
   int32_t* d_idx = (int32_t*)u;
@@ -5088,10 +5139,11 @@ int ks_unreserve(ks_ctx* ctx, const ks_pod_cols* pod, const ks_result* r, const 
   const int32_t node = r->node;
   HIPCHK(ctx, hipMemcpyAsync(d_idx, &node, 4, hipMemcpyHostToDevice, ctx->stream));
   if (cpuset) HIPCHK(ctx, hipMemcpyAsync(d_cs, cpuset, sizeof(CpuSet), hipMemcpyHostToDevice, ctx->stream));
-  int64_t na[2 * kNumaDev] = {0};
+  const int W = ctx->numa_w;
+  int64_t na[2 * kNumaWide] = {0};
   if (numa_alloc)
-    for (int k = 0; k < kNumaDev; ++k)
-      for (int q = 0; q < 2; ++q) na[q * kNumaDev + k] = numa_alloc[k * 2 + q];
+    for (int k = 0; k < W; ++k)
+      for (int q = 0; q < 2; ++q) na[q * W + k] = numa_alloc[k * 2 + q];
   HIPCHK(ctx, hipMemcpyAsync(d_na, na, sizeof(na), hipMemcpyHostToDevice, ctx->stream));
   // the node's reservation base restore follows the reservation's state: out before, back in after
   const bool rb = gi >= 0 && ctx->rsv_based;
@@ -5118,6 +5170,7 @@ int ks_unreserve(ks_ctx* ctx, const ks_pod_cols* pod, const ks_result* r, const 
   ua.cpu_loaded = ctx->cpu_loaded;
   ua.numa_pol = ctx->kc.numa_pol && ctx->numa_blob;
   ua.ratio_amp = ctx->cfg.numa.enable;
+  ua.numa_w = ctx->numa_w;
   ua.topo = ctx->cfg.topology.enable ? ctx->ast.topo : nullptr;
   ua.topo_props = ctx->ast.topo_props;
   ua.topo_count = ctx->topo_count;
@@ -5138,12 +5191,13 @@ int ks_fetch_numa_alloc(ks_ctx* ctx, int64_t* out, int32_t p) {
   if (p == 0) return KS_OK;
   memset(out, 0, (size_t)p * KS_MAX_NUMA * 2 * 8);
   if (!ctx->numa_alloc || ctx->cpuset_cap < p) return KS_OK;
-  std::vector<int64_t> h((size_t)p * 2 * kNumaDev);
+  const int W = ctx->numa_w;
+  std::vector<int64_t> h((size_t)p * 2 * W);
   HIPCHK(ctx, hipMemcpyAsync(h.data(), ctx->numa_alloc, h.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
   HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
   for (int32_t i = 0; i < p; ++i)
-    for (int k = 0; k < kNumaDev; ++k)
-      for (int q = 0; q < 2; ++q) out[((size_t)i * KS_MAX_NUMA + k) * 2 + q] = h[((size_t)i * 2 + q) * kNumaDev + k];
+    for (int k = 0; k < W; ++k)
+      for (int q = 0; q < 2; ++q) out[((size_t)i * KS_MAX_NUMA + k) * 2 + q] = h[((size_t)i * 2 + q) * W + k];
   return KS_OK;
 }
 

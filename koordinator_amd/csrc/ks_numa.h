@@ -20,9 +20,12 @@
 //     the node's whole CPUs) to add up to numCPUsNeeded), then DeviceShare's Allocate restricted to the affinity;
 //   * the node score over the allocated NUMA nodes (calculateAllocatableAndRequested, scoring.go:116-163; a
 //     cpu-bind pod's requested cpu is the node's amplified cpuset CPUs).
-// Up to kNumaDev NUMA nodes per node (15 masks); DeviceShare hints over at most 2 device NUMA nodes on nodes
-// with at most 2 NUMA nodes (ks_load_* refuses more); its identical per-resource lists merge as one list, so the
-// product is at most 15 x 15 permutations (3 x 3 x 3 with device hints).
+// Two widths, chosen per context at ks_load_numa_nodes: kNumaDev = 4 NUMA nodes per node (15 masks; this file's
+// register-resident path, used while no policy node has more) and kNumaWide = 8 (255 masks; ks_numa_wide.h).  The
+// width is a template parameter of the views, of NumaPolOutT and of the pass kernels (ks_pass.h), so both sets of
+// kernels live in one library.  DeviceShare hints over at most 2 device NUMA nodes on nodes with at most 2 NUMA
+// nodes (ks_load_* refuses more); its identical per-resource lists merge as one list, so the narrow product is at
+// most 15 x 15 permutations (3 x 3 x 3 with device hints), the wide one 255 x 255.
 // The oracle (oracle/koord_oracle.c numa_policy_eval, ko_merge_hints, dev_hints) restates the same code with
 // per-NUMA arrays and explicit hint lists; its merge is pinned by the reference's policy_test.go tables.
 #pragma once
@@ -32,17 +35,20 @@
 
 namespace ks {
 
-constexpr int kNumaDev = 4;  // NUMA nodes per node the device evaluates
+constexpr int kNumaDev = 4;   // NUMA nodes per node of the narrow path
+constexpr int kNumaWide = 8;  // ... of the wide path (= KS_MAX_NUMA)
 constexpr int kNumaMasks = (1 << kNumaDev) - 1;
 constexpr int kDevHintIds = 2;  // device-topology NUMA nodes DeviceShare hints are generated over
+static_assert(kNumaWide == KS_MAX_NUMA, "the wide path covers the ABI's NUMA nodes per node");
 
+// W below: the context's NUMA width (kNumaDev or kNumaWide); the columns hold W NUMA nodes per node
 struct DevNuma {
   const int32_t* count;  // [npad] NUMA nodes with resources
-  const int64_t* total;  // [2][kNumaDev][npad] amplified NUMANodeResources (cpu milli, memory)
-  int64_t* used;         // [2][kNumaDev][npad] allocatedResources (raw; mutable)
-  int64_t* off;          // [kNumaDev][npad] cpuset amplification of the allocated cpu: Amplify(cs) - cs (mutable)
-  int32_t* cs;           // [kNumaDev][npad] allocated cpuset CPUs on the NUMA node (mutable)
-  int32_t* free;         // [kNumaDev][npad] numa_free_word (ks_cpuset.h): CPUs of the NUMA node available to cpuset pods
+  const int64_t* total;  // [2][W][npad] amplified NUMANodeResources (cpu milli, memory)
+  int64_t* used;         // [2][W][npad] allocatedResources (raw; mutable)
+  int64_t* off;          // [W][npad] cpuset amplification of the allocated cpu: Amplify(cs) - cs (mutable)
+  int32_t* cs;           // [W][npad] allocated cpuset CPUs on the NUMA node (mutable)
+  int32_t* free;         // [W][npad] numa_free_word (ks_cpuset.h): CPUs of the NUMA node available to cpuset pods
                          // (bits 0-11), its whole free cores (12-21) and cores with a free CPU (22-31) (mutable)
   uint32_t* present;     // [npad] bit k: an allocatedResources entry exists (mutable)
   const uint32_t* flags; // [npad] ks_node_cols.numa_flags (policy in bits 5-6)
@@ -50,35 +56,44 @@ struct DevNuma {
 };
 
 // node view: HBM columns or the commit kernel's LDS copy
-struct NumaGView {
+template <int W>
+struct NumaGViewT {
+  static constexpr int kW = W;
   const DevNuma& d;
   int64_t n;
   __device__ __forceinline__ int policy() const { return (int)((gld(d.flags + n) >> KS_NUMA_POLICY_SHIFT) & 3u); }
   __device__ __forceinline__ int count() const { return gld(d.count + n); }
   __device__ __forceinline__ uint32_t present() const { return gld(d.present + n); }
-  __device__ __forceinline__ int64_t total(int r, int k) const { return gld(d.total + ((int64_t)r * kNumaDev + k) * d.npad + n); }
-  __device__ __forceinline__ int64_t used(int r, int k) const { return gld(d.used + ((int64_t)r * kNumaDev + k) * d.npad + n); }
+  __device__ __forceinline__ int64_t total(int r, int k) const { return gld(d.total + ((int64_t)r * W + k) * d.npad + n); }
+  __device__ __forceinline__ int64_t used(int r, int k) const { return gld(d.used + ((int64_t)r * W + k) * d.npad + n); }
   __device__ __forceinline__ int64_t off(int k) const { return gld(d.off + (int64_t)k * d.npad + n); }
   __device__ __forceinline__ int32_t freew(int k) const { return gld(d.free + (int64_t)k * d.npad + n); }
   __device__ __forceinline__ int32_t freec(int k) const { return freew(k) & 0xFFF; }
 };
+using NumaGView = NumaGViewT<kNumaDev>;
 
-// LDS slot words: [2K total | 2K used | K off | K (cs << 32 | free) | meta (policy | count << 8 | present << 32)]
-constexpr int kNumaWTot = 0, kNumaWUsed = 2 * kNumaDev, kNumaWOff = 4 * kNumaDev, kNumaWCpu = 5 * kNumaDev,
-              kNumaWMeta = 6 * kNumaDev;
-constexpr int kNumaSlotWords = 6 * kNumaDev + 1;
+// LDS slot words: [2W total | 2W used | W off | W (cs << 32 | free) | meta (policy | count << 8 | present << 32)]
+template <int W>
+struct NumaSlotT {
+  static constexpr int kTot = 0, kUsed = 2 * W, kOff = 4 * W, kCpu = 5 * W, kMeta = 6 * W, kWords = 6 * W + 1;
+};
+static_assert(NumaSlotT<kNumaWide>::kWords <= 64, "one lane of a wave per slot word");
 
-struct NumaLView {
+template <int W>
+struct NumaLViewT {
+  static constexpr int kW = W;
+  using S = NumaSlotT<W>;
   const int64_t* w;
-  __device__ __forceinline__ int policy() const { return (int)(w[kNumaWMeta] & 3); }
-  __device__ __forceinline__ int count() const { return (int)((w[kNumaWMeta] >> 8) & 0xFF); }
-  __device__ __forceinline__ uint32_t present() const { return (uint32_t)(w[kNumaWMeta] >> 32); }
-  __device__ __forceinline__ int64_t total(int r, int k) const { return w[kNumaWTot + r * kNumaDev + k]; }
-  __device__ __forceinline__ int64_t used(int r, int k) const { return w[kNumaWUsed + r * kNumaDev + k]; }
-  __device__ __forceinline__ int64_t off(int k) const { return w[kNumaWOff + k]; }
-  __device__ __forceinline__ int32_t freew(int k) const { return (int32_t)(uint32_t)w[kNumaWCpu + k]; }
+  __device__ __forceinline__ int policy() const { return (int)(w[S::kMeta] & 3); }
+  __device__ __forceinline__ int count() const { return (int)((w[S::kMeta] >> 8) & 0xFF); }
+  __device__ __forceinline__ uint32_t present() const { return (uint32_t)(w[S::kMeta] >> 32); }
+  __device__ __forceinline__ int64_t total(int r, int k) const { return w[S::kTot + r * W + k]; }
+  __device__ __forceinline__ int64_t used(int r, int k) const { return w[S::kUsed + r * W + k]; }
+  __device__ __forceinline__ int64_t off(int k) const { return w[S::kOff + k]; }
+  __device__ __forceinline__ int32_t freew(int k) const { return (int32_t)(uint32_t)w[S::kCpu + k]; }
   __device__ __forceinline__ int32_t freec(int k) const { return freew(k) & 0xFFF; }
 };
+using NumaLView = NumaLViewT<kNumaDev>;
 
 // a NUMA-node word's CPUs left by filterCPUsByRequiredCPUBindPolicy (resource_manager.go:595-627): FullPCPUs the CPUs
 // of the whole free cores, SpreadByPCPUs one CPU per core with a free CPU
@@ -96,17 +111,19 @@ struct NumaNodeCtx {
   uint32_t cores;   // the node's CoresWord (Cfg.cores: core counts, CPUsPerCore, CPU bind label; ks_device.h)
 };
 
-struct NumaPolOut {
+template <int W>
+struct NumaPolOutT {
   uint32_t reasons;
   int32_t score;
-  int64_t alloc[2][kNumaDev];  // the pod's NUMA allocation (cpu milli, memory)
-  int32_t cpus[kNumaDev];      // cpu-bind pod: CPUs allocateCPUSet takes per allocated NUMA node
+  int64_t alloc[2][W];  // the pod's NUMA allocation (cpu milli, memory)
+  int32_t cpus[W];      // cpu-bind pod: CPUs allocateCPUSet takes per allocated NUMA node
   uint32_t affinity;           // merged NUMANodeAffinity (0 = nil)
   bool admitted;               // Admit stored the affinity (DeviceShare's Filter / Score / Reserve read it)
   bool dev_done;               // reached DeviceShare's Allocate under the affinity (allow = affinity, or all if nil)
   bool dev_hit;                // ... and dev is its result (a hint's trial allocation, or computed without DEFER_DEV)
   DevOut dev;
 };
+using NumaPolOut = NumaPolOutT<kNumaDev>;
 
 // resourceAllocationScorer.score over cpu / memory with the plugin weights (scoring.go:206-242)
 __device__ __forceinline__ int32_t numa_res_score(const Cfg& c, bool most, int64_t rq_cpu, int64_t rq_mem,
@@ -239,8 +256,8 @@ template <typename T> struct LateDevHints { static constexpr bool value = true; 
 template <> struct LateDevHints<NoDevHints> { static constexpr bool value = false; };
 
 template <bool DEFER_DEV = false, typename V, typename DV, typename DHF = NoDevHints>
-__device__ __forceinline__ NumaPolOut numa_policy_eval(const Cfg& c, const PodRec& p, const V& v, const NumaNodeCtx& nc,
-                                                       const DV* dv, DHF dhf = DHF{}) {
+__device__ __forceinline__ NumaPolOut numa_policy_eval_narrow(const Cfg& c, const PodRec& p, const V& v,
+                                                              const NumaNodeCtx& nc, const DV* dv, DHF dhf = DHF{}) {
   constexpr bool LATE = LateDevHints<DHF>::value;
   NumaPolOut o;
   o.reasons = 0;
@@ -569,11 +586,25 @@ __device__ __forceinline__ NumaPolOut numa_policy_eval(const Cfg& c, const PodRe
   return o;
 }
 
+}  // namespace ks
+
+#include "ks_numa_wide.h"
+
+namespace ks {
+
+// the policy path at the view's width
+template <bool DEFER_DEV = false, typename V, typename DV, typename DHF = NoDevHints>
+__device__ __forceinline__ NumaPolOutT<V::kW> numa_policy_eval(const Cfg& c, const PodRec& p, const V& v,
+                                                               const NumaNodeCtx& nc, const DV* dv, DHF dhf = DHF{}) {
+  if constexpr (V::kW == kNumaWide) return numa_policy_eval_wide<DEFER_DEV>(c, p, v, nc, dv, dhf);
+  else return numa_policy_eval_narrow<DEFER_DEV>(c, p, v, nc, dv, dhf);
+}
+
 // Replace the policy-None NodeNUMAResource result of eval with the policy path's (the amplified-CPU filter and a
 // cpu-bind topology failure come first, plugin.go:275-338).
-template <bool DEBUG>
+template <bool DEBUG, int W>
 __device__ __forceinline__ void numa_policy_apply(const Cfg& c, const PodRec& p, EvalOut& o, uint32_t numa_rs,
-                                                  const NumaPolOut& pr) {
+                                                  const NumaPolOutT<W>& pr) {
   if (p.flags & kPodReqZero) return;
   if (numa_rs == 0) o.reasons |= DEBUG ? pr.reasons : (pr.reasons ? KS_R_FIT_PODS : 0u);
   o.total += (pr.score - o.numa) * c.numa_pw;

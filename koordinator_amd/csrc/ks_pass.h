@@ -76,7 +76,7 @@ struct SweepArgs {
 #ifndef KS_SWEEP_WAVES
 #define KS_SWEEP_WAVES 4  // (profiles/r03_sweep_w4_ab.txt: C5 sweep 51.1 -> 43.1 us per launch)
 #endif
-template <int NSC, int FEAT>
+template <int NSC, int FEAT, int NW = kNumaDev>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((FEAT == 0 && NSC <= 2) ? KS_SWEEP_WAVES : 1)))
 void sweep_kernel(SweepArgs a) {
   const int lane = threadIdx.x & 63;
@@ -126,7 +126,7 @@ void sweep_kernel(SweepArgs a) {
       const PodRec pod = load_pod_uniform(a.pods + cursor + p);
       EvalOut o = eval_full<NSC, false, true, FEAT>(
           a.c, pod, r, [&](auto&& f) { return f(RsvG<false>(*a.rv, node)); },
-          [&]() { return DevGView{*a.dv, node}; }, [&]() { return NumaGView{*a.nv, node}; });
+          [&]() { return DevGView{*a.dv, node}; }, [&]() { return NumaGViewT<NW>{*a.nv, node}; });
       const uint32_t key = o.reasons ? 0u : (((uint32_t)(key_total(a.c, o, NormM{0, 0, 0}) + 1) << 6) | (uint32_t)(63 - lane));
       t.x = wave_max_u32(key);
       t.y = wave_max_u32(key == t.x ? 0u : key);
@@ -198,7 +198,7 @@ void sweep_kernel(SweepArgs a) {
         const PodRec pod = load_pod_uniform(a.pods + cursor + p);
         EvalOut o = eval_full<NSC, false, true, FEAT>(
             a.c, pod, r, [&](auto&& f) { return f(RsvG<false>(*a.rv, node)); },
-            [&]() { return DevGView{*a.dv, node}; }, [&]() { return NumaGView{*a.nv, node}; });
+            [&]() { return DevGView{*a.dv, node}; }, [&]() { return NumaGViewT<NW>{*a.nv, node}; });
         if ((FEAT & 4) && a.c.stat) stat_eval(a.c, load_stat_uniform(a.pstat + cursor + p), st_hard, st_soft, st_lab, st_port, o);
         if ((FEAT & 4) && a.phase == 0) {
           // normalization maxima over the feasible nodes, witness = lowest index holding each
@@ -352,8 +352,9 @@ struct CommitArgs {
   int32_t total_pods, batch, k;
   int2* cpuset_list;   // (pod, node) of every cpu-bind Reserve, in placement order (ks_cpuset.h)
   int32_t* cpuset_n;
-  uint32_t* cpuset_split;  // [pod] CPUs per NUMA node of a cpu-bind Reserve on a NUMA-policy node (0 = whole node)
-  int64_t* numa_alloc;     // [pod][2][kNumaDev] NUMA-policy Reserve: the pod's NUMANodeResources (cpu milli, memory)
+  uint32_t* cpuset_split;  // [pod] CPUs per NUMA node of a cpu-bind Reserve on a NUMA-policy node (0 = whole node): 8 bits
+                           // each, one u32 per pod at NUMA width 4, one u64 at width 8
+  int64_t* numa_alloc;     // [pod][2][NW] NUMA-policy Reserve: the pod's NUMANodeResources (cpu milli, memory)
   int32_t force;           // ks_assume: the framework chose the node; no quota admission (Reserve only)
   int32_t rcap;        // reservations cached in LDS per slot (0 = none)
   int32_t rsv_bytes;   // LDS bytes of the slot reservation cache (commit_layout)
@@ -374,7 +375,7 @@ struct CommitArgs {
   unsigned long long* top_reset;
   // NUMA topology policy variants: Reserve's NodeNUMAResource / DeviceShare allocations on each pod's snapshot-best
   // nodes, computed before the commit by reserve_pre_kernel ([64][kPreRsvM]); NULL = the commit computes every Reserve
-  const struct PreRsv* pre_rsv;
+  const void* pre_rsv;  // PreRsvT<NW> records
   // PodTopologySpread / InterPodAffinity (ks_topo.h): 0 off; 1 the pass ends before its first topology pod; 2 the
   // topology step's one-pod commit; 3 ks_assume.  Every placed pod's properties are counted on its node.
   int32_t topo;
@@ -389,17 +390,19 @@ struct CommitArgs {
 // One pod's NodeNUMAResource + DeviceShare Reserve on one node of its snapshot ranking, computed on the snapshot state
 // (what the commit's Reserve computes on the slot state of a node no earlier pod of the pass touched).
 constexpr int kPreRsvM = 16;  // ranks per pod (C3: the winner is within the snapshot top-16 for 97.7% of pods)
-struct __attribute__((aligned(16))) PreRsv {
+template <int W>
+struct __attribute__((aligned(16))) PreRsvT {
   int32_t node;     // -1 = none
   uint32_t flags;   // bit 0: the node has a NUMA policy (npr valid), bit 1: npr.admitted
   uint32_t reasons, affinity;
-  int64_t alloc[2][kNumaDev];
-  int32_t cpus[kNumaDev];
+  int64_t alloc[2][W];
+  int32_t cpus[W];
   uint32_t gminors, rminors;
   int32_t _pad[2];
   int64_t g_core, g_mem, g_ratio, g_rdma;  // GpuReq per instance
 };
-static_assert(sizeof(PreRsv) == 144, "PreRsv layout");
+using PreRsv = PreRsvT<kNumaDev>;
+static_assert(sizeof(PreRsv) == 144 && sizeof(PreRsvT<kNumaWide>) == 224, "PreRsv layout");
 
 // The first pod of the pass after next: pass k+1 commits iff it was swept for the pods at the cursor this commit
 // leaves (rc), and then the pass after it starts behind its pods; otherwise pass k+1 is a bubble and k+2 starts at rc.
@@ -668,7 +671,7 @@ __device__ __forceinline__ Cands resolve_cands(const uint32_t* cand_chunk, const
 
 // Re-scan a candidate chunk's untouched nodes exactly for one pod (lane = node); touched nodes are
 // covered by the slot evaluation.
-template <int NSC, int FEAT>
+template <int NSC, int FEAT, int NW>
 __device__ __forceinline__ uint64_t rescan_untouched(const CommitArgs& a, const Cfg& cfg, const PodRec& pod,
                                                      int64_t chunk, uint64_t touched_mask, const NormM& M,
                                                      const PodStat* ps) {
@@ -688,7 +691,7 @@ __device__ __forceinline__ uint64_t rescan_untouched(const CommitArgs& a, const 
   }
   EvalOut o = eval_full<NSC, false, false, FEAT>(
       cfg, pod, r, [&](auto&& f) { return f(RsvG<false>(*a.rv, node)); },
-      [&]() { return DevGView{*a.dv, node}; }, [&]() { return NumaGView{*a.nv, node}; });
+      [&]() { return DevGView{*a.dv, node}; }, [&]() { return NumaGViewT<NW>{*a.nv, node}; });
   if ((FEAT & 4) && cfg.stat) stat_eval(cfg, *ps, sh, ss, sl, sp, o);
   const bool skip = o.reasons || ((touched_mask >> lane) & 1ull);
   return wave_max_u64(skip ? 0ull : gkey(key_total(cfg, o, M), node));
@@ -745,7 +748,7 @@ __device__ __forceinline__ void lds_rawtop(int64_t* rawtop, const uint64_t* cand
   }
 }
 
-template <int NSC, bool QC, int FEAT>
+template <int NSC, bool QC, int FEAT, int NW = kNumaDev>
 __global__ __launch_bounds__(commit_threads(FEAT)) void commit_kernel(CommitArgs a) {
   constexpr int NT = commit_threads(FEAT);
   constexpr bool RSV = (FEAT & 1) != 0;
@@ -779,7 +782,7 @@ __global__ __launch_bounds__(commit_threads(FEAT)) void commit_kernel(CommitArgs
   int64_t* sdev_tot = reinterpret_cast<int64_t*>(smem_raw + lay.sdev);
   int64_t* sdev_use = sdev_tot + kDevLdsStride * DW;
   int32_t* sdev_pres = reinterpret_cast<int32_t*>(sdev_use + kDevLdsStride * DU);
-  int64_t* snp = reinterpret_cast<int64_t*>(smem_raw + lay.snp);  // [slot][kNumaSlotWords]
+  int64_t* snp = reinterpret_cast<int64_t*>(smem_raw + lay.snp);  // [slot][NumaSlotT<NW>::kWords]
   // per slot: the node's dictionary-bit plugin words (taints hard, soft, labels, host ports -- the last one updated
   // by every Reserve of the pass): the last kMaxBatch * 32 B of the slot device region (dev_cache_bytes)
   // and before them the pass's PodStat records (Cfg.stat), and before those the normalization maxima table
@@ -1123,7 +1126,7 @@ __global__ __launch_bounds__(commit_threads(FEAT)) void commit_kernel(CommitArgs
   // Reservation: set once a commit of this pass lowered a node's restored Requested (the class -1 fast path is off then)
   bool rsv_raised = false;
   auto lookahead = [&](int32_t j) {
-    if ((FEAT & 8) && a.pre_rsv) pre_nodes = lane < kPreRsvM ? a.pre_rsv[j * kPreRsvM + lane].node : -1;
+    if ((FEAT & 8) && a.pre_rsv) pre_nodes = lane < kPreRsvM ? static_cast<const PreRsvT<NW>*>(a.pre_rsv)[j * kPreRsvM + lane].node : -1;
     // the fast path also holds for a pod without device requests when only DeviceShare's normalization
     // max made the profile non-monotone (its DeviceShare score is 0 on every node), and, with Reservation, for a pod
     // that matches no reservation: it sees every node through the base restore, whose Requested a commit only raises
@@ -1268,9 +1271,9 @@ __global__ __launch_bounds__(commit_threads(FEAT)) void commit_kernel(CommitArgs
         split[0] += t1 - t0;
         const DevLView dvl{sdev_tot + lane, sdev_use + lane, (uint32_t)sdev_pres[lane]};
         if ((FEAT & 8) && cfg.numa_pol && !(pod.flags & kPodReqZero)) {
-          const NumaLView nl{snp + lane * kNumaSlotWords};
+          const NumaLViewT<NW> nl{snp + lane * NumaSlotT<NW>::kWords};
           if (nl.policy() != 0) {
-            const NumaPolOut pr = (DEV && cfg.dev && (pod.flags & kPodHasGpu))
+            const NumaPolOutT<NW> pr = (DEV && cfg.dev && (pod.flags & kPodHasGpu))
                                       ? numa_policy_eval<true>(cfg, pod, nl, numa_node_ctx<NSC>(r), &dvl)
                                       : numa_policy_eval(cfg, pod, nl, numa_node_ctx<NSC>(r), (const DevLView*)nullptr);
             split_sink ^= (uint64_t)pr.score ^ pr.affinity ^ pr.reasons;
@@ -1316,7 +1319,7 @@ __global__ __launch_bounds__(commit_threads(FEAT)) void commit_kernel(CommitArgs
           return f(RsvG<true>(*a.rv, snode));
         };
         auto devf = [&]() { return DevLView{sdev_tot + lane, sdev_use + lane, (uint32_t)sdev_pres[lane]}; };
-        auto numaf = [&]() { return NumaLView{snp + lane * kNumaSlotWords}; };
+        auto numaf = [&]() { return NumaLViewT<NW>{snp + lane * NumaSlotT<NW>::kWords}; };
         if constexpr (HINTW) {
           // the slot's DeviceShare hints: the hint wave's (use_hw), else computed here
           auto dhf = [&]() -> DevHints {
@@ -1413,7 +1416,7 @@ __global__ __launch_bounds__(commit_threads(FEAT)) void commit_kernel(CommitArgs
         const uint64_t kmax = wave_max_u64(((need >> lane) & 1ull) ? cj.ub : 0ull);
         const int sel = __ffsll((long long)__ballot(((need >> lane) & 1ull) && cj.ub == kmax)) - 1;
         const int64_t c = (int64_t)(uint32_t)__shfl((int)cj.chunk, sel, 64);
-        const uint64_t v = rescan_untouched<NSC, FEAT>(a, cfg, pod, c, touched[c], Muse, &pst);
+        const uint64_t v = rescan_untouched<NSC, FEAT, NW>(a, cfg, pod, c, touched[c], Muse, &pst);
         ++rescans;
         best = umax64(best, v);
         need &= ~(1ull << sel);
@@ -1469,13 +1472,13 @@ __global__ __launch_bounds__(commit_threads(FEAT)) void commit_kernel(CommitArgs
       int64_t ld_numa = 0, ld_stat = 0, ld_dtot = 0, ld_duse = 0;
       if ((FEAT & 8) && cfg.numa_pol) {
         const DevNuma& nv = *a.nv;
-        if (lane < kNumaWUsed) ld_numa = gld(nv.total + (int64_t)lane * nv.npad + node);
-        else if (lane < kNumaWOff) ld_numa = gld(nv.used + (int64_t)(lane - kNumaWUsed) * nv.npad + node);
-        else if (lane < kNumaWCpu) ld_numa = gld(nv.off + (int64_t)(lane - kNumaWOff) * nv.npad + node);
-        else if (lane < kNumaWMeta)
-          ld_numa = ((int64_t)gld(nv.cs + (int64_t)(lane - kNumaWCpu) * nv.npad + node) << 32) |
-                    (int64_t)(uint32_t)gld(nv.free + (int64_t)(lane - kNumaWCpu) * nv.npad + node);
-        else if (lane == kNumaWMeta)
+        if (lane < NumaSlotT<NW>::kUsed) ld_numa = gld(nv.total + (int64_t)lane * nv.npad + node);
+        else if (lane < NumaSlotT<NW>::kOff) ld_numa = gld(nv.used + (int64_t)(lane - NumaSlotT<NW>::kUsed) * nv.npad + node);
+        else if (lane < NumaSlotT<NW>::kCpu) ld_numa = gld(nv.off + (int64_t)(lane - NumaSlotT<NW>::kOff) * nv.npad + node);
+        else if (lane < NumaSlotT<NW>::kMeta)
+          ld_numa = ((int64_t)gld(nv.cs + (int64_t)(lane - NumaSlotT<NW>::kCpu) * nv.npad + node) << 32) |
+                    (int64_t)(uint32_t)gld(nv.free + (int64_t)(lane - NumaSlotT<NW>::kCpu) * nv.npad + node);
+        else if (lane == NumaSlotT<NW>::kMeta)
           ld_numa = (int64_t)((gld(nv.flags + node) >> KS_NUMA_POLICY_SHIFT) & 3u) |
                     ((int64_t)gld(nv.count + node) << 8) | ((int64_t)gld(nv.present + node) << 32);
       }
@@ -1550,7 +1553,7 @@ __global__ __launch_bounds__(commit_threads(FEAT)) void commit_kernel(CommitArgs
       }
       // the slot's NUMA-node state (lane = word, NumaLView layout), dictionary words and device totals + topology /
       // used / present flag into LDS (loaded above)
-      if ((FEAT & 8) && cfg.numa_pol && lane < kNumaSlotWords) snp[s * kNumaSlotWords + lane] = ld_numa;
+      if ((FEAT & 8) && cfg.numa_pol && lane < NumaSlotT<NW>::kWords) snp[s * NumaSlotT<NW>::kWords + lane] = ld_numa;
       if (DEV && cfg.stat && lane < 4) sstat[4 * s + lane] = (uint64_t)ld_stat;
       if (DEV && cfg.dev) {
         if (lane < DW) sdev_tot[lane * kDevLdsStride + s] = ld_dtot;
@@ -1681,7 +1684,7 @@ __global__ __launch_bounds__(commit_threads(FEAT)) void commit_kernel(CommitArgs
         EvalOut e2 = eval_full<NSC, false, false, FEAT>(
             cfg, pod, n2, RsvWithOut<NSC, decltype(rv2)>{rv2, ro, dl},
             [&]() { return DevLView{sdev_tot + s, sdev_use + s, (uint32_t)sdev_pres[s]}; },
-            [&]() { return NumaLView{snp + s * kNumaSlotWords}; });
+            [&]() { return NumaLViewT<NW>{snp + s * NumaSlotT<NW>::kWords}; });
         if (DEV && cfg.stat) stat_eval(cfg, pst, sstat[4 * s], sstat[4 * s + 1], sstat[4 * s + 2], sstat[4 * s + 3], e2);
         fitla_pref = e2.total + norm_terms(cfg, e2, Muse);
       }
@@ -1757,18 +1760,18 @@ __global__ __launch_bounds__(commit_threads(FEAT)) void commit_kernel(CommitArgs
     uint32_t gminors = 0, rminors = 0;
     // NodeNUMAResource Reserve on a node with a NUMA policy: Allocate with the Filter's hint on the pre-pod state
     // (the topology manager's stored affinity also restricts DeviceShare's Reserve)
-    NumaPolOut npr;
+    NumaPolOutT<NW> npr;
     npr.admitted = false;
     npr.affinity = 0;
     bool npol = false;
     const bool want_npol = (FEAT & 8) && cfg.numa_pol && !(pflags & kPodReqZero);
     const bool want_dev = DEV && cfg.dev && (pflags & kPodHasGpu);
     // a slot created by this pod holds the snapshot state: reserve_pre_kernel's allocation for the node, if it ranked
-    const PreRsv* pre = nullptr;
+    const PreRsvT<NW>* pre = nullptr;
     const bool held_here = (FEAT & 16) && DEV && cfg.dev && RSV && cfg.rsv && ((uint32_t)sdev_pres[s] & kDevRsvHeld);
     if ((FEAT & 8) && a.pre_rsv && fresh && (want_npol || want_dev) && !held_here) {
       const uint64_t hit = __ballot(pre_nodes == node);  // (read by the look-ahead)
-      if (hit) pre = a.pre_rsv + j * kPreRsvM + (__ffsll((long long)hit) - 1);
+      if (hit) pre = static_cast<const PreRsvT<NW>*>(a.pre_rsv) + j * kPreRsvM + (__ffsll((long long)hit) - 1);
     }
     GpuReq g;
     if (pre) {
@@ -1778,7 +1781,7 @@ __global__ __launch_bounds__(commit_threads(FEAT)) void commit_kernel(CommitArgs
       npr.reasons = pre->reasons;
       npr.affinity = pre->affinity;
 #pragma unroll
-      for (int k = 0; k < kNumaDev; ++k) {
+      for (int k = 0; k < NW; ++k) {
         npr.alloc[0][k] = pre->alloc[0][k];
         npr.alloc[1][k] = pre->alloc[1][k];
         npr.cpus[k] = pre->cpus[k];
@@ -1791,7 +1794,7 @@ __global__ __launch_bounds__(commit_threads(FEAT)) void commit_kernel(CommitArgs
       g.rdma = pre->g_rdma;
       ++prehits;
     } else if (want_npol) {
-      const NumaLView nl{snp + s * kNumaSlotWords};
+      const NumaLViewT<NW> nl{snp + s * NumaSlotT<NW>::kWords};
       if (nl.policy() != 0) {
         PodRec pod = spods[j];
         pod.flags = pflags;
@@ -1847,60 +1850,61 @@ __global__ __launch_bounds__(commit_threads(FEAT)) void commit_kernel(CommitArgs
         gst(a.dv->used + (int64_t)lane * a.dv->npad + node, nv);  // the HBM table for the next pass
       }
     }
-    if ((FEAT & 8) && a.numa_alloc && lane < 2 * kNumaDev) {
+    if ((FEAT & 8) && a.numa_alloc && lane < 2 * NW) {
       int64_t v = 0;
 #pragma unroll
-      for (int q = 0; q < 2 * kNumaDev; ++q) v = (q == lane) ? npr.alloc[q / kNumaDev][q % kNumaDev] : v;
-      a.numa_alloc[(int64_t)(cursor0 + j) * 2 * kNumaDev + lane] = (npol && npr.reasons == 0) ? v : 0;
+      for (int q = 0; q < 2 * NW; ++q) v = (q == lane) ? npr.alloc[q / NW][q % NW] : v;
+      a.numa_alloc[(int64_t)(cursor0 + j) * 2 * NW + lane] = (npol && npr.reasons == 0) ? v : 0;
     }
-    uint32_t cpu_split = 0;  // cpu-bind pod: CPUs per NUMA node (8 bits each), 0 = takeCPUs over the whole node
+    using SplitT = std::conditional_t<NW == kNumaWide, uint64_t, uint32_t>;
+    SplitT cpu_split = 0;  // cpu-bind pod: CPUs per NUMA node (8 bits each), 0 = takeCPUs over the whole node
     if (npol && npr.reasons == 0) {
       // addPodAllocation: the NUMANodeResources to allocatedResources (node_allocation.go:86-99); a cpu-bind pod's
       // CPUs to the NUMA nodes' cpuset counts (and their amplification offsets) and available CPUs
-      int64_t* w = snp + s * kNumaSlotWords;
+      int64_t* w = snp + s * NumaSlotT<NW>::kWords;
       uint32_t bits = 0;
 #pragma unroll
-      for (int k = 0; k < kNumaDev; ++k) bits |= (npr.alloc[0][k] != 0 || npr.alloc[1][k] != 0) ? (1u << k) : 0u;
-      int32_t cpus[kNumaDev];
+      for (int k = 0; k < NW; ++k) bits |= (npr.alloc[0][k] != 0 || npr.alloc[1][k] != 0) ? (1u << k) : 0u;
+      int32_t cpus[NW];
 #pragma unroll
-      for (int k = 0; k < kNumaDev; ++k) cpus[k] = 0;
+      for (int k = 0; k < NW; ++k) cpus[k] = 0;
       if (cpubind) {
         if (bits) {
 #pragma unroll
-          for (int k = 0; k < kNumaDev; ++k) cpus[k] = npr.cpus[k];
+          for (int k = 0; k < NW; ++k) cpus[k] = npr.cpus[k];
         } else {
           cpus[0] = cpu_need;  // no NUMA allocation: admitted with a nil affinity, i.e. one NUMA node (count 1)
         }
 #pragma unroll
-        for (int k = 0; k < kNumaDev; ++k) cpu_split |= bits ? ((uint32_t)cpus[k] << (8 * k)) : 0u;
+        for (int k = 0; k < NW; ++k) cpu_split |= bits ? ((SplitT)(uint32_t)cpus[k] << (8 * k)) : (SplitT)0;
       }
-      const int rr = lane / kNumaDev, kk = lane % kNumaDev;
+      const int rr = lane / NW, kk = lane % NW;
       const double ratio = __longlong_as_double(snuma[4 * s + 2]);
-      if (lane < 2 * kNumaDev) {
+      if (lane < 2 * NW) {
         int64_t add = 0;
 #pragma unroll
-        for (int q = 0; q < 2 * kNumaDev; ++q) add = (q == lane) ? npr.alloc[q / kNumaDev][q % kNumaDev] : add;
+        for (int q = 0; q < 2 * NW; ++q) add = (q == lane) ? npr.alloc[q / NW][q % NW] : add;
         if (add != 0) {
-          const int64_t nvv = w[kNumaWUsed + lane] + add;
-          w[kNumaWUsed + lane] = nvv;
-          gst(a.nv->used + ((int64_t)rr * kNumaDev + kk) * a.nv->npad + node, nvv);
+          const int64_t nvv = w[NumaSlotT<NW>::kUsed + lane] + add;
+          w[NumaSlotT<NW>::kUsed + lane] = nvv;
+          gst(a.nv->used + ((int64_t)rr * NW + kk) * a.nv->npad + node, nvv);
         }
-      } else if (lane == 2 * kNumaDev && bits) {
-        const int64_t meta = w[kNumaWMeta] | ((int64_t)bits << 32);
-        w[kNumaWMeta] = meta;
+      } else if (lane == 2 * NW && bits) {
+        const int64_t meta = w[NumaSlotT<NW>::kMeta] | ((int64_t)bits << 32);
+        w[NumaSlotT<NW>::kMeta] = meta;
         gst(a.nv->present + node, (uint32_t)(meta >> 32));
-      } else if (lane >= 3 * kNumaDev && lane < 4 * kNumaDev) {
-        const int k = lane - 3 * kNumaDev;
+      } else if (lane >= 3 * NW && lane < 4 * NW) {
+        const int k = lane - 3 * NW;
         int32_t c = 0;
 #pragma unroll
-        for (int q = 0; q < kNumaDev; ++q) c = (q == k) ? cpus[q] : c;
+        for (int q = 0; q < NW; ++q) c = (q == k) ? cpus[q] : c;
         if (c != 0) {
-          const int64_t cw = w[kNumaWCpu + k];
+          const int64_t cw = w[NumaSlotT<NW>::kCpu + k];
           const int32_t cs1 = (int32_t)(cw >> 32) + c, fr1 = (int32_t)(uint32_t)cw - c;
           const int64_t m = (int64_t)cs1 * 1000;
           const int64_t off1 = ratio > 1.0 ? (int64_t)::ceil((double)m * ratio) - m : 0;
-          w[kNumaWCpu + k] = ((int64_t)cs1 << 32) | (int64_t)(uint32_t)fr1;
-          w[kNumaWOff + k] = off1;
+          w[NumaSlotT<NW>::kCpu + k] = ((int64_t)cs1 << 32) | (int64_t)(uint32_t)fr1;
+          w[NumaSlotT<NW>::kOff + k] = off1;
           gst(a.nv->cs + (int64_t)k * a.nv->npad + node, cs1);
           gst(a.nv->free + (int64_t)k * a.nv->npad + node, fr1);
           gst(a.nv->off + (int64_t)k * a.nv->npad + node, off1);
@@ -1921,7 +1925,7 @@ __global__ __launch_bounds__(commit_threads(FEAT)) void commit_kernel(CommitArgs
         snuma[4 * s + 3] -= cpu_need;
         if (cfg.cores) snuma[4 * s + 3] |= (int64_t)((uint64_t)kCoresDirty << 32);
         a.cpuset_list[atomicAdd(a.cpuset_n, 1)] = make_int2(cursor0 + j, node);
-        a.cpuset_split[cursor0 + j] = cpu_split;
+        reinterpret_cast<SplitT*>(a.cpuset_split)[cursor0 + j] = cpu_split;
       }
     }
     // NodePorts: NodeInfo.AddPod adds the pod's host ports (written back with the slot)
@@ -2047,7 +2051,7 @@ __global__ __launch_bounds__(commit_threads(FEAT)) void commit_kernel(CommitArgs
 // (DeviceShare Reserve) -- on the snapshot state, all ranks in parallel.  It runs on the commit's stream right before
 // the commit, so the state it reads is the state the commit loads into a new slot; the commit takes the record when
 // the pod lands on one of these nodes as a new slot and computes the Reserve itself otherwise.
-template <int FEAT>
+template <int FEAT, int NW = kNumaDev>
 __global__ __launch_bounds__(64) void reserve_pre_kernel(CommitArgs a) {
   constexpr bool DEV = (FEAT & 4) != 0;
   __shared__ int32_t sel[kPreRsvM];
@@ -2085,13 +2089,13 @@ __global__ __launch_bounds__(64) void reserve_pre_kernel(CommitArgs a) {
   if (kr && rr < kPreRsvM) sel[rr] = (int32_t)gkey_node(kr);
   __syncthreads();
   if (lane >= kPreRsvM) return;
-  PreRsv o;
+  PreRsvT<NW> o;
   o.node = sel[lane];
   o.flags = 0;
   o.reasons = 0;
   o.affinity = 0;
 #pragma unroll
-  for (int k = 0; k < kNumaDev; ++k) {
+  for (int k = 0; k < NW; ++k) {
     o.alloc[0][k] = o.alloc[1][k] = 0;
     o.cpus[k] = 0;
   }
@@ -2103,14 +2107,14 @@ __global__ __launch_bounds__(64) void reserve_pre_kernel(CommitArgs a) {
     const int64_t node = o.node;
     const PodRec pod = a.pods[cursor0 + j];
     const uint32_t pflags = pod.flags;
-    NumaPolOut npr;
+    NumaPolOutT<NW> npr;
     npr.admitted = false;
     npr.affinity = 0;
     npr.reasons = 0;
     bool npol = false;
     const DevGView dvg{*a.dv, node};
     if ((FEAT & 8) && cfg.numa_pol && !(pflags & kPodReqZero)) {
-      const NumaGView nv{*a.nv, node};
+      const NumaGViewT<NW> nv{*a.nv, node};
       if (nv.policy() != 0) {
         // the commit's slot copy of the node's cpuset state (RF_NUMA_* row fields)
         NumaNodeCtx nc;
@@ -2130,7 +2134,7 @@ __global__ __launch_bounds__(64) void reserve_pre_kernel(CommitArgs a) {
       o.reasons = npr.reasons;
       o.affinity = npr.affinity;
 #pragma unroll
-      for (int k = 0; k < kNumaDev; ++k) {
+      for (int k = 0; k < NW; ++k) {
         o.alloc[0][k] = npr.alloc[0][k];
         o.alloc[1][k] = npr.alloc[1][k];
         o.cpus[k] = npr.cpus[k];
@@ -2148,7 +2152,7 @@ __global__ __launch_bounds__(64) void reserve_pre_kernel(CommitArgs a) {
       o.g_rdma = g.rdma;
     }
   }
-  const_cast<PreRsv*>(a.pre_rsv)[j * kPreRsvM + lane] = o;
+  static_cast<PreRsvT<NW>*>(const_cast<void*>(a.pre_rsv))[j * kPreRsvM + lane] = o;
 }
 
 struct PassLaunch {
@@ -2174,5 +2178,12 @@ KS_DECLARE_VARIANT(15)
 KS_DECLARE_VARIANT(23)
 KS_DECLARE_VARIANT(31)
 #undef KS_DECLARE_VARIANT
+// the NUMA topology policy plugin sets at NUMA width 8 (ks_variant.hip with -DKS_NW=8)
+#define KS_DECLARE_WIDE(F) \
+  PassLaunch pass_launch_f##F##_n0_w8(); PassLaunch pass_launch_f##F##_n2_w8(); PassLaunch pass_launch_f##F##_n4_w8();
+KS_DECLARE_WIDE(11)
+KS_DECLARE_WIDE(14)
+KS_DECLARE_WIDE(15)
+#undef KS_DECLARE_WIDE
 
 }  // namespace ks

@@ -718,7 +718,7 @@ __device__ __forceinline__ EvalOut eval_full(const Cfg& c, const PodRec& p, Node
     const auto nv = numav();
     if (nv.policy() == 0) return ~0u;
     using DVT = decltype(devv());
-    NumaPolOut pr;
+    NumaPolOutT<decltype(nv)::kW> pr;
     if (dev_pod) {
       const DVT dv = devv();
       pr = numa_policy_eval<!DEBUG>(c, p, nv, numa_node_ctx<NSC>(r), &dv, dhf);

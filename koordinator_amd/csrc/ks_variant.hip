@@ -1,11 +1,21 @@
 // ks_variant.hip — one plugin-set (FEAT = KS_FEAT) x scalar-slot (NSC = KS_NSC) variant of the pass kernels (ks_pass.h) and its host launch
-// wrappers.  The Makefile compiles this file once per (FEAT, NSC) so the variants build in parallel.
+// wrappers.  The Makefile compiles this file once per (FEAT, NSC) so the variants build in parallel, and once more
+// with -DKS_NW=8 for the plugin sets with the NUMA topology policy path (FEAT & 8): the kernels at NUMA width 8
+// (ks_numa_wide.h).  KS_NW only picks the kernels' NW template argument and the name of the exported table; nothing in
+// the headers depends on it, so the objects define no entity twice.
 #include "ks_pass.h"
 #include "ks_mono.h"
 #include "ks_fq.h"
 
 #if !defined(KS_FEAT) || !defined(KS_NSC)
 #error "compile with -DKS_FEAT=<feature bits> -DKS_NSC=<0|2|4>"
+#endif
+
+#ifndef KS_NW
+#define KS_NW 4
+#endif
+#if KS_NW != 4 && !(KS_NW == 8 && (KS_FEAT & 8) != 0 && KS_FEAT != 31)
+#error "KS_NW is 4, or 8 for a plugin set with the NUMA topology policy path (KS_FEAT & 8) other than 31"
 #endif
 
 #define KS_CAT2(a, b) a##b
@@ -18,19 +28,21 @@ constexpr int F = KS_FEAT;
 
 constexpr int NSC = KS_NSC;
 
+constexpr int NW = KS_NW;
+
 hipError_t sweep(int blocks, hipStream_t s, const SweepArgs& a) {
-  hipLaunchKernelGGL((sweep_kernel<NSC, F>), dim3(blocks), dim3(256), 0, s, a);
+  hipLaunchKernelGGL((sweep_kernel<NSC, F, NW>), dim3(blocks), dim3(256), 0, s, a);
   return hipGetLastError();
 }
 
 hipError_t commit(bool qc, size_t smem, hipStream_t s, const CommitArgs& a) {
-  if (qc) hipLaunchKernelGGL((commit_kernel<NSC, true, F>), dim3(1), dim3(commit_threads(F)), smem, s, a);
-  else hipLaunchKernelGGL((commit_kernel<NSC, false, F>), dim3(1), dim3(commit_threads(F)), smem, s, a);
+  if (qc) hipLaunchKernelGGL((commit_kernel<NSC, true, F, NW>), dim3(1), dim3(commit_threads(F)), smem, s, a);
+  else hipLaunchKernelGGL((commit_kernel<NSC, false, F, NW>), dim3(1), dim3(commit_threads(F)), smem, s, a);
   return hipGetLastError();
 }
 
 hipError_t commit_attr(bool qc, size_t smem) {
-  const void* fn = qc ? (const void*)commit_kernel<NSC, true, F> : (const void*)commit_kernel<NSC, false, F>;
+  const void* fn = qc ? (const void*)commit_kernel<NSC, true, F, NW> : (const void*)commit_kernel<NSC, false, F, NW>;
   return hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
 }
 
@@ -62,14 +74,18 @@ hipError_t commit_fq_attr(bool keys, size_t smem) {
 
 #if (KS_FEAT & 8) != 0
 hipError_t reserve_pre(int blocks, hipStream_t s, const CommitArgs& a) {
-  hipLaunchKernelGGL((reserve_pre_kernel<F>), dim3(blocks), dim3(64), 0, s, a);
+  hipLaunchKernelGGL((reserve_pre_kernel<F, NW>), dim3(blocks), dim3(64), 0, s, a);
   return hipGetLastError();
 }
 #endif
 
 }  // namespace
 
+#if KS_NW == 8
+PassLaunch KS_CAT(KS_CAT(KS_CAT(KS_CAT(pass_launch_f, KS_FEAT), _n), KS_NSC), _w8)() {
+#else
 PassLaunch KS_CAT(KS_CAT(KS_CAT(pass_launch_f, KS_FEAT), _n), KS_NSC)() {
+#endif
 #if KS_FEAT == 0
   return PassLaunch{sweep, commit, commit_attr, commit_mono, commit_mono_attr, nullptr};
 #elif (KS_FEAT & 8) != 0

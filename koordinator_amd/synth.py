@@ -429,6 +429,47 @@ def make_numa_nodes(nodes: NodeTable, rng: np.random.Generator, policy_frac: flo
     return nn
 
 
+def make_numa_nodes_wide(nodes: NodeTable, rng: np.random.Generator, policy_frac: float = 0.5, cores=None,
+                         wide_frac: float = 0.7):
+    """make_numa_nodes with 5, 6, 7 or 8 NUMA nodes on wide_frac of the policy nodes (a dual-socket NPS4 host has
+    8) and 1, 2 or 4 on the rest: best-effort / restricted / single-numa-node in equal parts, the NUMA nodes
+    splitting the node's CPUs and memory, earlier pods' allocations on some of them."""
+    from .cluster import NumaNodes
+    n = nodes.n
+    cores = np.asarray(cores if cores is not None else nodes.alloc_milli_cpu // 1000)
+    nn = NumaNodes(n)
+    pol = np.where(rng.random(n) < policy_frac, rng.integers(1, 4, n), 0).astype(np.uint32)
+    nodes.numa_flags[:] = (nodes.numa_flags & ~np.uint32(3 << abi.KS_NUMA_POLICY_SHIFT)) | (pol << abi.KS_NUMA_POLICY_SHIFT)
+    cnt = np.where(rng.random(n) < wide_frac, rng.integers(5, 9, n), rng.choice(np.array([1, 2, 4]), n))
+    for i in range(n):
+        if pol[i] == 0:
+            continue
+        k = int(cnt[i])
+        nn.count[i] = k
+        nn.alloc_cpu[i, :k] = int(cores[i]) * 1000 // k
+        nn.alloc_memory[i, :k] = int(nodes.alloc_memory[i]) // k
+        for j in range(k):
+            if rng.random() < 0.5:
+                f = rng.random() * 0.6
+                nn.used_cpu[i, j] = int(nn.alloc_cpu[i, j] * f) // 1000 * 1000
+                nn.used_memory[i, j] = int(nn.alloc_memory[i, j] * f) // MI * MI
+                nn.used_present[i, j] = 1
+    return nn
+
+
+def scale_pods(pods: PodTable, rng: np.random.Generator, frac: float = 0.3, factor: int = 8) -> PodTable:
+    """cpu and memory requests (and their LoadAware estimates) x factor on a fraction of the pods: requests that
+    no single NUMA node of a many-NUMA host holds"""
+    big = rng.random(pods.n) < frac
+    for col in ("req_milli_cpu", "req_memory", "nonzero_milli_cpu", "nonzero_memory", "la_req_cpu", "la_lim_cpu",
+                "la_req_memory", "la_lim_memory"):
+        v = getattr(pods, col)
+        v[:] = np.where(big, v * factor, v)
+    for slot in (SLOT_BATCH_CPU, SLOT_BATCH_MEMORY):
+        pods.req_scalar[slot] = np.where(big, pods.req_scalar[slot] * factor, pods.req_scalar[slot])
+    return pods
+
+
 def policy_numa_nodes(nodes: NodeTable, cpus: CpuState, policy_mask, rng: np.random.Generator, cores,
                       policy: int = abi.KS_NUMA_POLICY_SINGLE_NUMA_NODE) -> "NumaNodes":
     """NodeResourceTopology zones of the policy nodes, consistent with their CPU state: two NUMA nodes (the
