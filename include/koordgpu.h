@@ -25,7 +25,8 @@
  *                      followed by Reserve (framework_extender.go:457; load_aware.go:260;
  *                      elasticquota/plugin.go:323), for a batch of pods in queue order,
  *                      with exact one-pod-at-a-time semantics.
- *   ks_eval_pod        one pod's Filter + Score over every node without Reserve
+ *   ks_eval_pod        one pod's Filter + Score over every node without Reserve (ks_eval_pod_summary: the same,
+ *                      reduced on the device to the feasible set, the winner, the FitError counts and the top rows)
  *   ks_assume          Reserve of one pod on the node the framework chose; ks_unreserve its Unreserve
  *                      (framework_extender.go:204 RunFilterPluginsWithNominatedPods,
  *                      :237 RunScorePlugins) — the parity/debug entry point.
@@ -49,7 +50,7 @@
 extern "C" {
 #endif
 
-#define KS_ABI_VERSION 10
+#define KS_ABI_VERSION 11
 
 #define KS_MAX_SCALARS 4 /* scalar (extended) resource slots, e.g. kubernetes.io/batch-cpu */
 #define KS_QUOTA_DIMS 8  /* resource dimensions tracked by ElasticQuota admission */
@@ -749,8 +750,9 @@ typedef struct ks_ctx ks_ctx;
  * .so whose score-matrix width or struct sizes differ writes past the caller's buffers): out[0] = KS_ABI_VERSION,
  * out[1] = KS_NUM_SCORE_PLUGINS, then sizeof ks_config, ks_node_cols, ks_pod_cols, ks_quota_cols, ks_quota_tree,
  * ks_reservation_cols, ks_device_cols, ks_cpu_topology, ks_cpu_state_cols, ks_numa_node_cols, ks_result,
- * ks_node_state, ks_stats, ks_node_pod_cols, ks_preempt_result (KS_ABI_LAYOUT_WORDS words; n < that fills the first n).  Returns KS_ABI_LAYOUT_WORDS. */
-#define KS_ABI_LAYOUT_WORDS 17
+ * ks_node_state, ks_stats, ks_node_pod_cols, ks_preempt_result, ks_pod_summary (KS_ABI_LAYOUT_WORDS words; n < that
+ * fills the first n).  Returns KS_ABI_LAYOUT_WORDS. */
+#define KS_ABI_LAYOUT_WORDS 18
 int ks_abi_layout(int64_t *out, int32_t n);
 
 /* Returns KS_OK and *out on success.  On failure *out is NULL and
@@ -882,6 +884,42 @@ int ks_eval_pod(ks_ctx *ctx, const ks_pod_cols *pod, uint32_t *reasons, int64_t 
 /* the same entry under its round-1 name */
 int ks_eval_pod_debug(ks_ctx *ctx, const ks_pod_cols *pod, uint32_t *reasons, int64_t *scores,
                       int64_t *total);
+
+/* ks_eval_pod reduced on the device (ABI 11): what a shim that owns the cycle needs of one pod's evaluation -- the
+ * feasible set (PreFilterResult.NodeNames, O(1) Filter answers), selectHost's winner under this ABI's lowest-index
+ * tie-break, the per-reason node counts of the FitError message ("0/N nodes are available: ..."), the nodes whose
+ * status is UnschedulableAndUnresolvable (ks_preempt's `unresolvable`) and the first rows of the --debug-scores
+ * table -- without copying the n x KS_NUM_SCORE_PLUGINS matrix to the host. */
+#define KS_SUMMARY_MAX_TOP 64
+typedef struct ks_pod_summary {
+  int64_t nodes;            /* nodes evaluated (= what ks_eval_pod covers on this context) */
+  int64_t feasible;         /* nodes with reasons == 0 */
+  int64_t unresolvable;     /* nodes with (reasons & unresolvable_mask) != 0 */
+  int64_t reason_nodes[32]; /* [b] = nodes whose reasons word has bit b (KS_R_* = 1u << b) set: a node with two
+                               reasons counts under both, as upstream's FitError counts a status with two reasons */
+  int64_t best_total;       /* total of best_node; -1 when none */
+  int32_t best_node;        /* argmax of total over feasible nodes, lowest index on ties; -1 when none */
+  int32_t top_count;        /* min(top_n, feasible) rows written to the top_* outputs */
+} ks_pod_summary;
+
+/* Evaluates pod 0 of `pod` exactly as ks_eval_pod does (same validation, refusals and KS_ESTATE before
+ * ks_load_nodes; the evaluation is the same launch sequence) and reduces the result on the device.  The top rows
+ * are ordered by total descending, then node index ascending; best_node == top_nodes[0] whenever top_n >= 1 and
+ * feasible >= 1.  The library carries no table of which KS_R_* bits are unresolvable: the shim supplies
+ * unresolvable_mask (0: unresolvable = 0 and all-zero bits).  The bitmasks pack node i into bit i % 64 of word
+ * i / 64; bits at and above n in the last word are 0.  Any of the five array outputs may be NULL (not written).
+ * KS_EINVAL: top_n < 0, top_n > KS_SUMMARY_MAX_TOP, out == NULL, or top_n > 0 with all three top_* pointers NULL.
+ * With no nodes loaded (n == 0) the summary is zeros with best_node = best_total = -1.  Copies to the host: the
+ * struct, top_count rows and the requested mask words; the device scratch lives with the context (a call at an
+ * unchanged node count allocates nothing).  On a sharded context (ks_shard_init*) the summary covers what
+ * ks_eval_pod covers there; merging the ranks' summaries is not done by the library. */
+int ks_eval_pod_summary(ks_ctx *ctx, const ks_pod_cols *pod, uint32_t unresolvable_mask, int32_t top_n,
+                        ks_pod_summary *out,
+                        int32_t *top_nodes,   /* [top_n]            or NULL */
+                        int64_t *top_totals,  /* [top_n]            or NULL */
+                        int64_t *top_scores,  /* [top_n][KS_NUM_SCORE_PLUGINS], un-weighted, or NULL */
+                        uint64_t *feasible_bits,      /* [(n+63)/64], bit i%64 of word i/64 = node i feasible, or NULL */
+                        uint64_t *unresolvable_bits); /* same packing, (reasons & mask) != 0, or NULL */
 
 /* Reserve of pod 0 of `pod` on `node`, which the framework chose: every enabled plugin's Reserve
  * (load_aware.go:260; elasticquota/plugin.go:323-335; reservation/plugin.go:532-570 with NominateReservation on

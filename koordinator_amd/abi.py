@@ -8,7 +8,7 @@ from __future__ import annotations
 
 import ctypes as C
 
-KS_ABI_VERSION = 10
+KS_ABI_VERSION = 11
 KS_MAX_SCALARS = 4
 KS_QUOTA_DIMS = 8
 KS_MAX_GPUS = 8
@@ -506,6 +506,7 @@ EXPORTED_SYMBOLS = [
     "ks_restore",
     "ks_eval_pod_debug",
     "ks_eval_pod",
+    "ks_eval_pod_summary",
     "ks_assume",
     "ks_unreserve",
     "ks_fetch_numa_alloc",
@@ -572,4 +573,22 @@ class KsPreemptResult(C.Structure):
         ("candidates", C.c_int32),
         ("potential_nodes", C.c_int32),
     ]
-KS_ABI_LAYOUT_WORDS = 17
+
+
+# ---- per-pod evaluation summary (ks_eval_pod_summary) ----
+KS_SUMMARY_MAX_TOP = 64
+
+
+class KsPodSummary(C.Structure):
+    _fields_ = [
+        ("nodes", C.c_int64),
+        ("feasible", C.c_int64),
+        ("unresolvable", C.c_int64),
+        ("reason_nodes", C.c_int64 * 32),
+        ("best_total", C.c_int64),
+        ("best_node", C.c_int32),
+        ("top_count", C.c_int32),
+    ]
+
+
+KS_ABI_LAYOUT_WORDS = 18

@@ -37,6 +37,7 @@
 #include "ks_debug.h"
 #include "ks_topo.h"
 #include "ks_preempt.h"
+#include "ks_summary.h"
 
 using namespace ks;
 
@@ -1013,6 +1014,10 @@ struct ks_ctx {
   int64_t* numa_alloc = nullptr;  // [cpuset_cap][2][numa_w] NUMA-policy allocation per pod of the last call
   void* evbuf = nullptr;          // ks_eval_pod scratch, kept across calls
   size_t evbuf_bytes = 0;
+  void* sumbuf = nullptr;         // ks_eval_pod_summary scratch (sum_buffers), kept across calls like evbuf
+  size_t sumbuf_bytes = 0;
+  void* sumhost = nullptr;        // ... its pinned host copy: the summary, the top rows, the bitmask words
+  size_t sumhost_bytes = 0;
   void* ures = nullptr;           // ks_unreserve scratch: node index, the pod's cpuset and NUMA allocation
   void* rdscratch = nullptr;      // ks_read_nodes: the NodeInfo view of the reservation-restored columns
   std::vector<int32_t> h_rsv_gi;  // caller reservation row -> CSR position
@@ -1290,7 +1295,8 @@ int ks_abi_layout(int64_t* out, int32_t n) {
       KS_ABI_VERSION, KS_NUM_SCORE_PLUGINS, sizeof(ks_config), sizeof(ks_node_cols), sizeof(ks_pod_cols),
       sizeof(ks_quota_cols), sizeof(ks_quota_tree), sizeof(ks_reservation_cols), sizeof(ks_device_cols),
       sizeof(ks_cpu_topology), sizeof(ks_cpu_state_cols), sizeof(ks_numa_node_cols), sizeof(ks_result),
-      sizeof(ks_node_state), sizeof(ks_stats), sizeof(ks_node_pod_cols), sizeof(ks_preempt_result)};
+      sizeof(ks_node_state), sizeof(ks_stats), sizeof(ks_node_pod_cols), sizeof(ks_preempt_result),
+      sizeof(ks_pod_summary)};
   for (int32_t i = 0; out && i < n && i < KS_ABI_LAYOUT_WORDS; ++i) out[i] = v[i];
   return KS_ABI_LAYOUT_WORDS;
 }
@@ -1466,6 +1472,8 @@ void ks_destroy(ks_ctx* ctx) {
   for (PodStage* ps : {&ctx->st, &ctx->est, &ctx->ast})
     if (ps->h_pack) (void)hipHostFree(ps->h_pack);
   dev_free(ctx->evbuf);
+  dev_free(ctx->sumbuf);
+  if (ctx->sumhost) (void)hipHostFree(ctx->sumhost);
   dev_free(ctx->ures);
   dev_free(ctx->rdscratch);
   dev_free(ctx->dscratch);
@@ -4855,16 +4863,17 @@ int ks_update_reservation_usage(ks_ctx* ctx, const int32_t* rows, const int64_t*
   return done(KS_OK);
 }
 
-int ks_eval_pod(ks_ctx* ctx, const ks_pod_cols* pod, uint32_t* reasons, int64_t* scores, int64_t* total) {
-  if (!ctx || !pod) return ctx ? (ctx->err = "ks_eval_pod: bad args", KS_EINVAL) : KS_EINVAL;
-  if (!ctx->node_blob) KS_FAIL(ctx, KS_ESTATE, "ks_eval_pod before ks_load_nodes");
+// One pod's evaluation on ctx->stream into the context's evaluation buffer (ks_eval_pod and ks_eval_pod_summary):
+// validation, staging, the evaluation kernel and every normalization; eb's dr / ds / dt hold the result once the
+// stream reaches this point.  Nothing is copied back and the stream is not synchronized.
+static int eval_pod_launch(ks_ctx* ctx, const ks_pod_cols* pod, const char* who, EvBuf& eb) {
+  if (!ctx->node_blob) KS_FAIL(ctx, KS_ESTATE, "%s before ks_load_nodes", who);
   if (int rc = validate_pods(ctx, pod, 1); rc != KS_OK) return rc;
   bind_mode(ctx, ctx->val_bind_required);
   HIPCHK(ctx, hipSetDevice(ctx->device));
   if (ensure_stage(ctx, ctx->est, 1) != KS_OK) return KS_ENOMEM;
   if (stage_cols(ctx, ctx->est, pod, 1) != KS_OK || prep_stage(ctx, ctx->est, 1) != KS_OK) return KS_EHIP;
   const int64_t n = ctx->n;
-  EvBuf eb;
   if (ev_buffers(ctx, eb) != KS_OK) return KS_ENOMEM;
   uint32_t* dr = eb.dr;
   int64_t* ds = eb.ds;
@@ -4900,6 +4909,16 @@ int ks_eval_pod(ks_ctx* ctx, const ks_pod_cols* pod, uint32_t* reasons, int64_t*
                          ctx->cfg.reservation.plugin_weight);
   }
   HIPCHK(ctx, hipGetLastError());
+  return KS_OK;
+}
+
+int ks_eval_pod(ks_ctx* ctx, const ks_pod_cols* pod, uint32_t* reasons, int64_t* scores, int64_t* total) {
+  if (!ctx || !pod) return ctx ? (ctx->err = "ks_eval_pod: bad args", KS_EINVAL) : KS_EINVAL;
+  EvBuf eb;
+  if (int rc = eval_pod_launch(ctx, pod, "ks_eval_pod", eb); rc != KS_OK) return rc;
+  const int64_t n = ctx->n;
+  const uint32_t* dr = eb.dr;
+  const int64_t *ds = eb.ds, *dt = eb.dt;
   if (reasons && n) HIPCHK(ctx, hipMemcpyAsync(reasons, dr, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream));
   if (scores && n) HIPCHK(ctx, hipMemcpyAsync(scores, ds, (size_t)n * 8 * KS_NUM_SCORE_PLUGINS, hipMemcpyDeviceToHost, ctx->stream));
   if (total && n) HIPCHK(ctx, hipMemcpyAsync(total, dt, (size_t)n * 8, hipMemcpyDeviceToHost, ctx->stream));
@@ -4909,6 +4928,90 @@ int ks_eval_pod(ks_ctx* ctx, const ks_pod_cols* pod, uint32_t* reasons, int64_t*
 
 int ks_eval_pod_debug(ks_ctx* ctx, const ks_pod_cols* pod, uint32_t* reasons, int64_t* scores, int64_t* total) {
   return ks_eval_pod(ctx, pod, reasons, scores, total);
+}
+
+// ks_eval_pod_summary's scratch for the loaded node count, device and pinned host, grown like ev_buffers' (never per
+// call at an unchanged n).  Device: SumOut, the feasible and the unresolvable words (those three are the one copy
+// back), then the workgroups' partial totals, bins and partial nodes.
+struct SumBuf {
+  SumOut* out;
+  uint64_t *fbits, *ubits;
+  int64_t* part_tot;
+  uint32_t* blk_bins;
+  int32_t* part_idx;
+  int64_t nwords;
+  int blocks;
+};
+static int sum_buffers(ks_ctx* ctx, SumBuf& b) {
+  static_assert(sizeof(SumOut) % 8 == 0, "the bitmask words follow SumOut");
+  const int64_t n = ctx->n;
+  b.nwords = (n + 63) / 64;
+  b.blocks = (int)((n + kSumThreads - 1) / kSumThreads);
+  const size_t host_bytes = sizeof(SumOut) + (size_t)b.nwords * 16;
+  const size_t bytes = host_bytes + (size_t)b.blocks * (kSumTop * 12 + kSumBins * 4) + 64;
+  if (ctx->sumbuf_bytes < bytes) {
+    dev_free(ctx->sumbuf);
+    ctx->sumbuf_bytes = 0;
+    if (dev_alloc(ctx, &ctx->sumbuf, bytes) != KS_OK) return KS_ENOMEM;
+    ctx->sumbuf_bytes = bytes;
+  }
+  if (ctx->sumhost_bytes < host_bytes) {
+    if (ctx->sumhost) (void)hipHostFree(ctx->sumhost);
+    ctx->sumhost = nullptr;
+    ctx->sumhost_bytes = 0;
+    HIPCHK(ctx, hipHostMalloc(&ctx->sumhost, host_bytes, hipHostMallocDefault));
+    ctx->sumhost_bytes = host_bytes;
+  }
+  b.out = (SumOut*)ctx->sumbuf;
+  b.fbits = (uint64_t*)(b.out + 1);
+  b.ubits = b.fbits + b.nwords;
+  b.part_tot = (int64_t*)(b.ubits + b.nwords);
+  b.blk_bins = (uint32_t*)(b.part_tot + (size_t)b.blocks * kSumTop);
+  b.part_idx = (int32_t*)(b.blk_bins + (size_t)b.blocks * kSumBins);
+  return KS_OK;
+}
+
+int ks_eval_pod_summary(ks_ctx* ctx, const ks_pod_cols* pod, uint32_t unresolvable_mask, int32_t top_n,
+                        ks_pod_summary* out, int32_t* top_nodes, int64_t* top_totals, int64_t* top_scores,
+                        uint64_t* feasible_bits, uint64_t* unresolvable_bits) {
+  if (!ctx || !pod) return ctx ? (ctx->err = "ks_eval_pod_summary: bad args", KS_EINVAL) : KS_EINVAL;
+  if (!out) KS_FAIL(ctx, KS_EINVAL, "ks_eval_pod_summary: out is NULL");
+  if (top_n < 0 || top_n > KS_SUMMARY_MAX_TOP)
+    KS_FAIL(ctx, KS_EINVAL, "ks_eval_pod_summary: top_n %d outside [0, %d]", top_n, KS_SUMMARY_MAX_TOP);
+  if (top_n > 0 && !top_nodes && !top_totals && !top_scores)
+    KS_FAIL(ctx, KS_EINVAL, "ks_eval_pod_summary: top_n %d without a top_nodes, top_totals or top_scores buffer", top_n);
+  EvBuf eb;
+  if (int rc = eval_pod_launch(ctx, pod, "ks_eval_pod_summary", eb); rc != KS_OK) return rc;
+  const int64_t n = ctx->n;
+  memset(out, 0, sizeof(*out));
+  out->best_node = -1;
+  out->best_total = -1;
+  if (n == 0) {
+    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+    return KS_OK;
+  }
+  SumBuf sb;
+  if (int rc = sum_buffers(ctx, sb); rc != KS_OK) return rc;
+  const int32_t k = top_n > 1 ? top_n : 1;  // the winner is row 0 whatever top_n is
+  hipLaunchKernelGGL(summary_block_kernel, dim3((unsigned)sb.blocks), dim3(kSumThreads), 0, ctx->stream, n, eb.dr, eb.dt,
+                     unresolvable_mask, k, sb.fbits, sb.ubits, sb.blk_bins, sb.part_tot, sb.part_idx);
+  hipLaunchKernelGGL(summary_merge_kernel, dim3(1), dim3(kSumMergeWaves * 64), 0, ctx->stream, n, (int32_t)sb.blocks,
+                     top_n, k, sb.blk_bins, sb.part_tot, sb.part_idx, eb.ds, sb.out);
+  HIPCHK(ctx, hipGetLastError());
+  // one copy: the summary and the top rows, and the bitmask words up to the last one asked for
+  const size_t words = unresolvable_bits ? 2 * (size_t)sb.nwords : feasible_bits ? (size_t)sb.nwords : 0;
+  HIPCHK(ctx, hipMemcpyAsync(ctx->sumhost, sb.out, sizeof(SumOut) + words * 8, hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+  const SumOut* h = (const SumOut*)ctx->sumhost;
+  *out = h->s;
+  const size_t rows = (size_t)h->s.top_count;
+  if (top_nodes) memcpy(top_nodes, h->top_nodes, rows * 4);
+  if (top_totals) memcpy(top_totals, h->top_totals, rows * 8);
+  if (top_scores) memcpy(top_scores, h->top_scores, rows * 8 * KS_NUM_SCORE_PLUGINS);
+  const uint64_t* hb = (const uint64_t*)(h + 1);
+  if (feasible_bits) memcpy(feasible_bits, hb, (size_t)sb.nwords * 8);
+  if (unresolvable_bits) memcpy(unresolvable_bits, hb + sb.nwords, (size_t)sb.nwords * 8);
+  return KS_OK;
 }
 
 // Unreserve of every plugin + the scheduler cache's ForgetPod for one pod (ks_unreserve; one thread, a few dozen

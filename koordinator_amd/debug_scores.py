@@ -74,3 +74,70 @@ def eval_debug_table(ev, cfg, pod, node_names, top_n: int, pod_ref: str):
     if len(feas) < 2:
         return None
     return debug_scores(top_n, pod_ref, per_plugin, [node_names[i] for i in feas])
+
+
+# FitError text of each reason bit (index b = KS_R_* bit 1 << b), from the comments next to the KS_R_* defines in
+# include/koordgpu.h: the quoted status message where the comment quotes one, the reference's error name otherwise.
+REASON_TEXT = [
+    "Too many pods",
+    "Insufficient cpu",
+    "Insufficient memory",
+    "Insufficient ephemeral-storage",
+    "Insufficient <scalar>",
+    "ErrReasonUsageExceedThreshold cpu",
+    "ErrReasonUsageExceedThreshold memory",
+    "ErrReasonAggregatedUsageExceedThreshold",
+    "filterProdUsage",
+    "ErrReasonReservationAffinity",
+    "filterWithReservations: no matched reservation satisfies the pod",
+    "ErrInsufficientAmplifiedCPU",
+    "ErrInvalidCPUAmplificationRatio",
+    "Insufficient gpu devices",
+    "node has no (healthy) GPU",
+    "ErrInvalidCPUTopology",
+    "node(s) NUMA Topology affinity error",
+    "Insufficient NUMA <resource>",
+    "node(s) missing NUMA resources",
+    "Insufficient rdma devices",
+    "node(s) Joint-Allocate rules not met",
+    "not enough cpus available to satisfy request",
+    "ErrInvalidRequestedCPUs",
+    "ErrCPUBindPolicyConflict",
+    "ErrSMTAlignmentError",
+    "node(s) had untolerated taint",
+    "node(s) didn't match Pod's node affinity/selector",
+    "node(s) didn't have free ports for the requested pod ports",
+    "node(s) didn't match pod topology spread constraints",
+    "node(s) didn't match pod affinity rules",
+    "node(s) didn't match pod anti-affinity rules",
+    "node(s) didn't satisfy existing pods anti-affinity rules",
+]
+
+
+def fit_error_message(n_nodes: int, reason_nodes, reason_text=REASON_TEXT) -> str:
+    """The scheduler's FitError text for a pod no node fits, "0/N nodes are available: <count> <reason>, ... .", from
+    ks_eval_pod_summary's histogram (reason_nodes[b] = nodes whose reasons word has bit b): one "<count> <reason>"
+    per non-empty bin, sorted as strings before they are joined, as upstream's FitError.Error does.  A node with two
+    reasons counts under both.  KS_R_LA_AGGREGATED and KS_R_LA_PROD qualify the LoadAware bits and are listed like any
+    other bin.  Parity unpinned: upstream's framework/types.go is not on disk, so the sentence's exact form (the
+    prefix, ", " between reasons, the closing ".") is this project's reading of it, and the texts of the bins whose
+    header comment names an error constant instead of quoting a message are those names."""
+    parts = sorted(f"{int(c)} {reason_text[b]}" for b, c in enumerate(reason_nodes) if int(c) > 0)
+    msg = f"0/{int(n_nodes)} nodes are available"
+    return msg + (": " + ", ".join(parts) + "." if parts else ".")
+
+
+def eval_debug_table_top(ev, cfg, pod, node_names, top_n: int, pod_ref: str):
+    """eval_debug_table from the device's own reduction (Evaluator.eval_pod_summary): the top_n rows, already in the
+    table's order (total descending, equal totals in node order), are all that leaves the device.  None under the same
+    conditions; top_n above KS_SUMMARY_MAX_TOP is served by eval_debug_table."""
+    if top_n <= 0:
+        return None
+    if top_n > abi.KS_SUMMARY_MAX_TOP:
+        return eval_debug_table(ev, cfg, pod, node_names, top_n, pod_ref)
+    s = ev.eval_pod_summary(pod, top_n=top_n)
+    if s["feasible"] < 2:
+        return None
+    rows = [int(i) for i in s["top_nodes"]]
+    _, per_plugin = plugin_scores(cfg, np.zeros(len(rows), np.uint32), s["top_scores"])
+    return debug_scores(top_n, pod_ref, per_plugin, [node_names[i] for i in rows])

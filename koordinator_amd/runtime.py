@@ -80,6 +80,8 @@ def lib() -> C.CDLL:
     L.ks_restore.argtypes = [vp]
     L.ks_eval_pod_debug.argtypes = [vp, C.POINTER(abi.KsPodCols), abi.PU32, abi.P64, abi.P64]
     L.ks_eval_pod.argtypes = [vp, C.POINTER(abi.KsPodCols), abi.PU32, abi.P64, abi.P64]
+    L.ks_eval_pod_summary.argtypes = [vp, C.POINTER(abi.KsPodCols), C.c_uint32, C.c_int32, C.POINTER(abi.KsPodSummary),
+                                      abi.P32, abi.P64, abi.P64, abi.PU64, abi.PU64]
     L.ks_assume.argtypes = [vp, C.POINTER(abi.KsPodCols), C.c_int32, C.POINTER(abi.KsResult), abi.PU64, abi.P64]
     L.ks_unreserve.argtypes = [vp, C.POINTER(abi.KsPodCols), C.POINTER(abi.KsResult), abi.PU64, abi.P64]
     L.ks_fetch_numa_alloc.argtypes = [vp, abi.P64, C.c_int32]
@@ -115,7 +117,7 @@ def expected_layout() -> list:
     return [abi.KS_ABI_VERSION, abi.KS_NUM_SCORE_PLUGINS] + [C.sizeof(t) for t in (
         abi.KsConfig, abi.KsNodeCols, abi.KsPodCols, abi.KsQuotaCols, abi.KsQuotaTree, abi.KsReservationCols,
         abi.KsDeviceCols, abi.KsCpuTopology, abi.KsCpuStateCols, abi.KsNumaNodeCols, abi.KsResult, abi.KsNodeState,
-        abi.KsStats, abi.KsNodePodCols, abi.KsPreemptResult)]
+        abi.KsStats, abi.KsNodePodCols, abi.KsPreemptResult, abi.KsPodSummary)]
 
 
 def check_layout(L) -> None:
@@ -383,6 +385,37 @@ class Evaluator:
                                      scores.ctypes.data_as(abi.P64), total.ctypes.data_as(abi.P64)))
         n = self.n
         return reasons[:n], scores[: n * abi.KS_NUM_SCORE_PLUGINS].reshape(n, abi.KS_NUM_SCORE_PLUGINS), total[:n]
+
+    def eval_pod_summary(self, pod: PodTable, top_n: int = 0, unresolvable_mask: int = 0, want_bits: bool = False):
+        """ks_eval_pod reduced on the device (ks_eval_pod_summary): a dict of nodes, feasible, unresolvable,
+        reason_nodes (int64[32], [b] = nodes with reason bit b), best_node / best_total (-1 when nothing fits), and the
+        first top_count = min(top_n, feasible) nodes by (total descending, node ascending) as top_nodes, top_totals and
+        top_scores [top_count, KS_NUM_SCORE_PLUGINS] (un-weighted).  want_bits adds feasible_bits and unresolvable_bits
+        (uint64 words, node i = bit i % 64 of word i // 64).  Nothing of size n x plugins leaves the device."""
+        top_n = int(top_n)
+        rows = min(max(top_n, 1), abi.KS_SUMMARY_MAX_TOP)  # (an invalid top_n is the library's to refuse)
+        s = abi.KsPodSummary()
+        nodes = np.zeros(rows, np.int32)
+        totals = np.zeros(rows, np.int64)
+        scores = np.zeros((rows, abi.KS_NUM_SCORE_PLUGINS), np.int64)
+        words = max((self.n + 63) // 64, 1)
+        fbits = np.zeros(words, np.uint64) if want_bits else None
+        ubits = np.zeros(words, np.uint64) if want_bits else None
+        cols = pod.ks()
+        self._chk(self.L.ks_eval_pod_summary(
+            self.h, C.byref(cols), int(unresolvable_mask) & 0xFFFFFFFF, top_n, C.byref(s),
+            nodes.ctypes.data_as(abi.P32), totals.ctypes.data_as(abi.P64), scores.ctypes.data_as(abi.P64),
+            fbits.ctypes.data_as(abi.PU64) if want_bits else None,
+            ubits.ctypes.data_as(abi.PU64) if want_bits else None))
+        k = int(s.top_count)
+        out = {"nodes": int(s.nodes), "feasible": int(s.feasible), "unresolvable": int(s.unresolvable),
+               "reason_nodes": np.array(s.reason_nodes[:], np.int64), "best_node": int(s.best_node),
+               "best_total": int(s.best_total), "top_nodes": nodes[:k], "top_totals": totals[:k],
+               "top_scores": scores[:k]}
+        if want_bits:
+            out["feasible_bits"] = fbits[: (self.n + 63) // 64]
+            out["unresolvable_bits"] = ubits[: (self.n + 63) // 64]
+        return out
 
     def assume(self, pod: PodTable, node: int):
         """Reserve of pod 0 on `node` (the framework's choice): (result record, cpuset words, NUMA allocation
