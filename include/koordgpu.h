@@ -770,6 +770,28 @@ int ks_create(const ks_config *cfg, ks_ctx **out);
 void ks_destroy(ks_ctx *ctx);
 const char *ks_last_error(const ks_ctx *ctx);
 
+/* ---- Reusing a context.  A context lives as long as the scheduler process: tables are loaded again on every
+ * resync, in whatever order the informers fire.  After any sequence of loads the context behaves as a context created
+ * fresh and given the current tables (tests/test_gpu_context_reuse.py):
+ *   - ks_load_nodes replaces the node table and drops every table indexed by node: reservations, devices, CPU state,
+ *     the NUMA-node table and the node-pod table (ks_preempt answers KS_ESTATE until ks_load_node_pods), and with them
+ *     everything derived per node.  It drops the checkpoint: ks_restore answers KS_ESTATE until the next
+ *     ks_checkpoint.  It drops the staged batch (validated and flagged against the old nodes): ks_schedule_staged
+ *     answers KS_ESTATE until the next ks_stage_pods; ks_schedule stages its own pods and is not affected.
+ *   - ks_load_nodes keeps the quota table with its usage (quotas are not indexed by node), the shard setup
+ *     (ks_shard_init) and the pipeline mode (ks_set_pipeline).
+ *   - The tables that follow ks_load_nodes -- ks_load_reservations, ks_load_devices, ks_load_cpu_state,
+ *     ks_load_numa_nodes, and ks_load_quotas at any time -- may be loaded in any order; none needs another to be
+ *     there.  A table that is never loaded is empty: no reservations, no device information, no CPU topology, no NUMA
+ *     resources on the policy nodes.  Each of them before the first ks_load_nodes is KS_ESTATE ("... before
+ *     ks_load_nodes"), except ks_load_quotas.
+ *   - A ks_load_X replaces table X whole, the effect of earlier commits on it included, and leaves every other table
+ *     as it stands.  A checkpoint taken before it describes the old table: ks_checkpoint again after a batch of loads
+ *     before the next ks_restore (as after the ks_update_* deltas).  ks_load_quotas with fewer rows than a staged
+ *     batch was validated against drops that batch like ks_load_nodes does.
+ *   - A load that is refused (KS_EINVAL, KS_EUNSUPPORTED) for a combination of tables the library does not model,
+ *     such as reservations holding devices next to a policy node with more than 4 NUMA nodes, leaves a context that
+ *     takes further loads; load the refused table, or ks_load_nodes, again before scheduling. ---- */
 int ks_load_nodes(ks_ctx *ctx, const ks_node_cols *nodes, int64_t n);
 /* Informer deltas: rows[i] replaces node idx[i]; arrays in `rows` have length m. */
 int ks_update_nodes(ks_ctx *ctx, const int32_t *idx, const ks_node_cols *rows, int64_t m);

@@ -1100,6 +1100,7 @@ struct ks_ctx {
   bool cpu_bind_required = false;    // the current operation's pods include a required CPU bind policy
   bool val_bind_required = false;    // ... set by the last successful validate_pods
   bool staged_bind_required = false; // ... of the staged batch (ks_stage_pods)
+  bool staged_stale = false;         // a reload dropped the staged batch: ks_schedule_staged is KS_ESTATE until ks_stage_pods
   bool cpusets_clobbered = false;    // ks_assume reused the batch's cpuset / NUMA buffers since the last schedule
   // nodes with device pods placed by ks_assume and not yet ks_unreserve'd: their Unreserve re-derives the
   // per-instance request from the node's device totals, so ks_update_devices must not change those meanwhile
@@ -1851,6 +1852,40 @@ int ks_load_nodes(ks_ctx* ctx, const ks_node_cols* nodes, int64_t n) {
   ctx->rsv_nrows = 0;
   ctx->rsv_live = 0;
   ctx->rmir = ks_ctx::RsvMirror{};
+  ctx->h_rsv_gi.clear();
+  ctx->h_rsv_node.clear();
+  ctx->rsv_perm.clear();
+  ctx->h_dev_held.assign((size_t)n, 0);  // ... and with it what its rows held: no node's devices are held
+  ctx->dev_held_any = false;
+  // the other tables indexed by node go with the old nodes (include/koordgpu.h "Reusing a context"): the device
+  // table, the CPU state and the NUMA-node table with its width, and the per-node host caches derived from them, at
+  // the new node count before the first helper below indexes them (dev_apply_held, check_dev_numa, numa_refresh_free)
+  dev_free(ctx->dev_blob);
+  ctx->dv = DevDev{};
+  ctx->dev_used_ckpt = nullptr;
+  ctx->dev_loaded = false;
+  ctx->h_dev_ids.assign((size_t)n, 0);
+  ctx->h_dev_assumed_ckpt.clear();
+  dev_free(ctx->cpu_blob);
+  ctx->cpu = DevCpu{};
+  ctx->cpu_ckpt = nullptr;
+  ctx->cpu_loaded = false;
+  ctx->cpu_cpc.clear();
+  ctx->h_topos.clear();
+  ctx->h_topo_dense.clear();
+  ctx->h_cpu_nn.assign((size_t)n, 0);
+  dev_free(ctx->numa_blob);
+  ctx->nv = DevNuma{};
+  ctx->numa_ckpt = nullptr;
+  ctx->numa_w = kNumaDev;
+  ctx->numa_policy_nodes = 0;
+  ctx->h_numa_k.assign((size_t)n, 0);
+  // scratch sized by the old padded node count, allocated again on demand
+  dev_free(ctx->rdscratch);
+  // a staged batch was validated and flagged (kPodNormDyn, the scalar width) against the old nodes, and the last
+  // call's results, cpusets and NUMA allocations belong to them: ks_schedule_staged refuses until ks_stage_pods
+  ctx->staged_stale = ctx->staged_stale || ctx->np > 0;
+  ctx->np = 0;
   // the node-pod table (ks_load_node_pods) is indexed by the old node rows and its per-call scratch is sized to the
   // old node count: drop it, so ks_preempt returns KS_ESTATE until it is reloaded for these nodes
   dev_free(ctx->npod_blob);
@@ -1922,12 +1957,14 @@ int ks_load_nodes(ks_ctx* ctx, const ks_node_cols* nodes, int64_t n) {
   }
   cores_mode(ctx);
   if (cores_refresh(ctx) != KS_OK) return KS_EHIP;
-  dev_free(ctx->numa_blob);
   if (ctx->numa_policy_nodes > 0) {
     if (numa_install(ctx, nullptr, nullptr, nullptr) != KS_OK) return KS_EHIP;
     ctx->kc.numa_pol = 1;
     ctx->kc.monotone = 0;  // a Reserve can move a node's best NUMA hint: keys are not monotone
     ctx->kc.monotone_nd = 0;
+  } else {
+    // no policy node: the device copy describes no table either (not the dropped one's freed columns)
+    HIPCHK(ctx, hipMemcpyAsync(ctx->dnv, &ctx->nv, sizeof(DevNuma), hipMemcpyHostToDevice, ctx->stream));
   }
   HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
   return KS_OK;
@@ -3017,6 +3054,15 @@ int ks_load_quotas(ks_ctx* ctx, const ks_quota_cols* qc, int32_t nq) {
     while (cur >= 0 && steps <= nq) cur = parent[cur], ++steps;
     if (cur >= 0) KS_FAIL(ctx, KS_EINVAL, "quota %d: parent chain has a cycle", i);
   }
+  // the table is valid: a blob of its size for it (the one allocated above is released again); a table refused
+  // above has already replaced the loaded one's blob, so load a valid table before scheduling (include/koordgpu.h)
+  dev_free(ctx->quota_blob);
+  if (dev_alloc(ctx, &ctx->quota_blob, bytes) != KS_OK) {
+    ctx->q = DevQuotas{};
+    return KS_ENOMEM;
+  }
+  // a staged batch's quota rows were checked against the old row count (validate_pods)
+  if (ctx->np > 0 && nq < ctx->q.q) ctx->staged_stale = true;
   HIPCHK(ctx, hipMemcpyAsync(ctx->quota_blob, h.data(), bytes, hipMemcpyHostToDevice, ctx->stream));
   char* d = (char*)ctx->quota_blob;
   ctx->q.q = nq;
@@ -3509,6 +3555,7 @@ int ks_stage_pods(ks_ctx* ctx, const ks_pod_cols* pods, int32_t p) {
   if (ensure_stage(ctx, ctx->st, p) != KS_OK) return KS_ENOMEM;
   if (p > 0 && stage_cols(ctx, ctx->st, pods, p) != KS_OK) return KS_EHIP;
   ctx->np = p;
+  ctx->staged_stale = false;
   ctx->staged_bind_required = ctx->val_bind_required;
   HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
   return KS_OK;
@@ -4392,6 +4439,8 @@ static int launch_pass(ks_ctx* ctx, int32_t ppw, int sweep_blocks, const PipeSha
 
 static int schedule_staged_impl(ks_ctx* ctx) {
   if (!ctx->node_blob) KS_FAIL(ctx, KS_ESTATE, "schedule before ks_load_nodes");
+  if (ctx->staged_stale)
+    KS_FAIL(ctx, KS_ESTATE, "ks_schedule_staged: the staged batch predates a table reload; call ks_stage_pods again");
   HIPCHK(ctx, hipSetDevice(ctx->device));
   bind_mode(ctx, ctx->staged_bind_required);
   ctx->cpusets_clobbered = false;
@@ -5316,10 +5365,9 @@ int ks_read_nodes(ks_ctx* ctx, ks_node_state* o) {
   // the restored columns (the live columns are never touched)
   DevNodes v = ctx->d;
   if (ctx->rsv_based && n) {
-    const size_t bytes = n * 8 * (5 + KS_MAX_SCALARS);
+    // [5 + KS_MAX_SCALARS][npad]: sized by this node table's padded count (ks_load_nodes frees it with the old table)
     if (!ctx->rdscratch && dev_alloc(ctx, &ctx->rdscratch, (size_t)ctx->npad * 8 * (5 + KS_MAX_SCALARS)) != KS_OK)
       return KS_ENOMEM;
-    (void)bytes;
     int64_t* sc = (int64_t*)ctx->rdscratch;
     int64_t** cols[5 + KS_MAX_SCALARS] = {&v.req_cpu, &v.req_mem, &v.req_eph, &v.nz_cpu, &v.nz_mem};
     for (int k = 0; k < KS_MAX_SCALARS; ++k) cols[5 + k] = &v.req_sc[k];

@@ -233,6 +233,7 @@ class Evaluator:
         cols = nodes.ks()
         self._chk(self.L.ks_load_nodes(self.h, C.byref(cols), nodes.n))
         self.n = nodes.n
+        self.nr = 0  # (the library drops the reservation table with the old nodes)
         self.nprops = int(np.asarray(nodes.topo_count).shape[0])
 
     def update_nodes(self, idx, rows: NodeTable):
