@@ -15,9 +15,11 @@
 //  * no Reservation / NUMA / DeviceShare / dictionary state, no normalization, no cpu-bind Reserve, no ks_assume.
 //
 // KEYS = true (the slot-key table fits the LDS): a slow pod's keys on the touched slots are not evaluated
-// by wave 0 (lane = slot, one full evaluation's latency per slow pod) but ahead of time by wave 2, the evaluator:
-// whenever a slot row changes, it evaluates that one row for every pod of the pass (lane = pod) into
-// skey[slot][pod].  Wave 0's slow path is then a wait for the evaluator, one LDS read and the wave max.
+// by wave 0 (lane = slot, one full evaluation's latency per slow pod) but ahead of time by the helper waves: whenever
+// a slot row changes, one of them evaluates that one row for every pod of the pass (lane = pod) into
+// skey[slot][pod].  Waves 1 and 2 share the descriptor queue by entry (even / odd); the one that takes a new slot's
+// descriptor builds the row from the prefetched raw row and evaluates it at once (one hand-off), each has its own
+// `handled` counter.  Wave 0's slow path is then a wait for both counters, one LDS read and the wave max.
 #pragma once
 
 #include "ks_pass.h"
@@ -71,14 +73,25 @@ __global__ __launch_bounds__(commit_threads(0)) void commit_fq_kernel(CommitArgs
   QuotaRowsLds qview = quota_lds(smem_raw + lay.quota, a.q.q);
   QuotaRowsLds* qlds = &qview;
   unsigned long long* touched = reinterpret_cast<unsigned long long*>(smem_raw + lay.touched);
-  // [issue order] {node, slot | pod << 8 | second << 16 | built << 17}: one descriptor per row change.  Wave 1 builds
-  // the row of every descriptor without `built`; with KEYS wave 2 evaluates the row of every descriptor (`built`: the
-  // row is wave 0's own work, a miss's new row or a Reserve onto a touched slot, finished before the descriptor is
-  // issued; without KEYS no such descriptor is issued).  A pod issues at most one, so kMaxBatch entries suffice.
+  // [issue order] {node, slot | pod << 8 | second << 16 | built << 17}: one descriptor per row change.  Without
+  // `built` the slot is new and its row was prefetched (rawtop / rawrun): a helper wave builds it and sets its ready
+  // bit.  `built` (KEYS only): the row is wave 0's own work, a miss's new row or a Reserve onto a touched slot,
+  // finished before the descriptor is issued.  With KEYS the helper that takes a descriptor also evaluates its row,
+  // so a prefetched new slot costs wave 0 one hand-off; waves 1 and 2 take the even and the odd entries, each with
+  // its own `handled` counter.  A pod issues at most one descriptor, so kMaxBatch entries suffice.
+  //
+  // Exactness of two evaluators.  Entries of different slots are independent.  A slot's first descriptor
+  // is its creation; every later one comes from a slow pod's Reserve onto the slot, and that Reserve runs after the
+  // pod's wait_keys, which covers every descriptor issued so far, the creation and every earlier Reserve included.
+  // So the two helpers never write the same skey row concurrently, no helper reads a row while term_take changes it,
+  // and when wave 0 has seen both counters reach their shares of its issue count, skey[s][j] is pod j's key on slot s
+  // after every pod before j.
   int2* hdesc = reinterpret_cast<int2*>(smem_raw + lay.help);
   int32_t* hpend = reinterpret_cast<int32_t*>(smem_raw + lay.help + (size_t)kMaxBatch * 8);  // descriptors issued
   int32_t* hdone = hpend + 1;                                                                // wave 0 is done
-  int32_t* heval = hpend + 2;                                                                // descriptors evaluated
+  // {even entries handled by wave 1, odd entries handled by wave 2}: an aligned pair, so wait_keys polls both with
+  // one 8-byte LDS read (each half has one writer, which stores its 4 bytes)
+  int32_t* heval = hpend + 2;
   uint32_t* skey = reinterpret_cast<uint32_t*>(smem_raw + lay.skey);  // [slot][kSlotKeyStride] (KEYS)
   unsigned long long* hready = reinterpret_cast<unsigned long long*>(smem_raw + lay.help + (size_t)kMaxBatch * 8 + 16);
   const int tid = threadIdx.x;
@@ -93,8 +106,9 @@ __global__ __launch_bounds__(commit_threads(0)) void commit_fq_kernel(CommitArgs
   if (np == 0) return;  // a topology pod at the cursor: the next topology step takes it
 #ifdef KS_COMMIT_STAMPS
   // diagnostic build: commit_kernel's stamp points (tools/diag_commit.py), except that the admission is part of the
-  // look-ahead's slot 1 and slot 6 is the slow path's wait (KEYS: for the evaluator, else for the builder) plus the
-  // loop's exit, so slot 2 is the evaluation (KEYS: the key read) and the wave max alone
+  // look-ahead's slot 1 and slot 6 is the slow path's wait (KEYS: for both helpers' keys, else for the builder's rows)
+  // plus the loop's exit, so slot 2 is the evaluation (KEYS: the key read) and the wave max alone.  The slots mean
+  // what they meant when wave 2 alone evaluated.
   uint64_t ph[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   uint64_t tlast = __builtin_amdgcn_s_memtime();
 #define KS_FSTAMP(i)                                   \
@@ -168,11 +182,13 @@ __global__ __launch_bounds__(commit_threads(0)) void commit_fq_kernel(CommitArgs
   if (tid == 0) {
     *hpend = 0;
     *hdone = 0;
-    *heval = 0;
+    heval[0] = 0;
+    heval[1] = 0;
     *hready = 0ull;
   }
   __syncthreads();
-  // the other waves are done; wave 0 runs the sequential loop, wave 1 builds slot rows, wave 2 evaluates them (KEYS)
+  // the other waves are done; wave 0 runs the sequential loop, wave 1 builds slot rows; KEYS: waves 1 and 2 build
+  // and evaluate them
   if (tid >= (KEYS ? 192 : 128)) return;
   KS_FSTAMP(0);
   // Opaque copies of the profile words this plugin set reads: hipcc otherwise re-loads kernel-argument words inside
@@ -254,71 +270,59 @@ __global__ __launch_bounds__(commit_threads(0)) void commit_fq_kernel(CommitArgs
     }
   };
 
-  if (KEYS && tid >= 128) {
-    // ---- wave 2: the slot-key evaluator (lane = pod).  It takes the descriptors in issue order, so when wave 0 has
-    // seen `heval` reach the number it issued, skey[s][j] is pod j's key on slot s after every pod before j.  Wave 0
-    // changes a row it did not just create (term_take) only in a slow pod's Reserve, which comes after that pod's wait
-    // for every descriptor issued so far: the evaluator never reads a row that is being changed.  Nobody reads the
-    // table once wave 0 is done, so the wave leaves as soon as it sees `hdone`. ----
-    const int32_t pl = min(lane, np - 1);
-    const PodRec pod = spods[pl];
-    int32_t next = 0;
+  if (tid >= 64) {
+    // ---- the helper waves, one loop.  Without KEYS wave 1 takes every descriptor and builds its row.  With KEYS
+    // wave 1 takes the even entries and wave 2 the odd ones: a helper builds the row of a descriptor without `built`,
+    // publishes its ready bit (the write-back and a later Reserve onto the slot wait for it), then evaluates the row
+    // for the pods after the issuing one (lane = pod) and bumps its `handled` counter.  For a row it built itself its
+    // reads follow its own writes: DS operations of one wave, no cross-wave acquire, so a new slot costs wave 0 one
+    // hand-off.  Splitting by entry and not by kind keeps both helpers busy in a run of fast pods, where every
+    // descriptor is a build plus an evaluation and wave 0 issues them faster than one wave handles them.
+    // Exit: nobody reads the table once wave 0 is done, so after `hdone` a helper skips the evaluations; it still
+    // builds every row among its entries (the write-back reads them), and leaves when it has seen `hdone` and then no
+    // entry of its own below `hpend` (wave 0 issues nothing after `hdone`). ----
+    const int32_t me = KEYS && tid >= 128 ? 1 : 0;
+    const PodRec pod = spods[min(lane, np - 1)];  // (KEYS: lane = pod; unused otherwise)
+    int32_t next = me, handled = 0;
     for (;;) {
-      if (__builtin_amdgcn_readfirstlane(__hip_atomic_load(hdone, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP))) break;
       const int32_t pend =
           __builtin_amdgcn_readfirstlane(__hip_atomic_load(hpend, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP));
       if (next >= pend) {
+        if (__builtin_amdgcn_readfirstlane(__hip_atomic_load(hdone, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP)) &&
+            next >= __builtin_amdgcn_readfirstlane(__hip_atomic_load(hpend, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP)))
+          break;
         __builtin_amdgcn_s_sleep(1);
         continue;
       }
       const int32_t w = __builtin_amdgcn_readfirstlane(hdesc[next].y);
+      // (`hdone` read with the descriptor: a stale 0 only costs an evaluation nobody reads)
+      const bool eval =
+          KEYS && !__builtin_amdgcn_readfirstlane(__hip_atomic_load(hdone, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP));
       const int32_t s = w & 0xFF, jj = (w >> 8) & 0xFF;
-      if (!((w >> 17) & 1) &&
-          !((readlane64(__hip_atomic_load(hready, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP), 0) >> s) & 1ull)) {
-        __builtin_amdgcn_s_sleep(1);  // wave 1 is still building the row
-        continue;
-      }
-      NodeReg<NSC> r;
-      slot_to_reg<NSC>(rows[s], r);  // wave-uniform address: LDS broadcast reads
-      const EvalOut o = eval_pod_node<NSC, false>(cfg, pod, r);
-      if (lane > jj && lane < np) skey[s * kSlotKeyStride + lane] = o.reasons == 0 ? (uint32_t)(o.total + 1) : 0u;
-      ++next;
-      if (lane == 0) __hip_atomic_store(heval, next, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
-    }
-    return;
-  }
-  if (tid >= 64) {
-    // ---- wave 1: the slot-row builder (runs until wave 0 is done and every descriptor is built) ----
-    int32_t next = 0;
-    for (;;) {
-      const int32_t pend =
-          __builtin_amdgcn_readfirstlane(__hip_atomic_load(hpend, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP));
-      if (next < pend) {
-        const int2 d = hdesc[next];
-        const int32_t w = __builtin_amdgcn_readfirstlane(d.y);
-        if (KEYS && ((w >> 17) & 1)) {  // wave 0 built or changed this row itself: the evaluator's descriptor only
-          ++next;
-          continue;
-        }
-        const int32_t s = w & 0xFF, jj = (w >> 8) & 0xFF;
+      if (!KEYS || !((w >> 17) & 1)) {
         const int64_t* src = (((w >> 16) & 1) ? rawrun : rawtop) + jj * 32;
         const uint32_t pflags = __builtin_amdgcn_readfirstlane(spods[jj].flags);
         build_row(&rows[s], src, reinterpret_cast<const int64_t*>(&spods[jj]), pflags);
         if (lane == 0)
           __hip_atomic_fetch_or(hready, 1ull << s, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
-        ++next;
-        continue;
+        // the evaluation below reads what other lanes of this wave wrote: keep the compiler from moving its reads up
+        if (KEYS) __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
       }
-      if (__builtin_amdgcn_readfirstlane(__hip_atomic_load(hdone, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP)) &&
-          next >= __builtin_amdgcn_readfirstlane(__hip_atomic_load(hpend, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP)))
-        break;
-      __builtin_amdgcn_s_sleep(1);
+      next += KEYS ? 2 : 1;
+      if (eval) {
+        NodeReg<NSC> r;
+        slot_to_reg<NSC>(rows[s], r);  // wave-uniform address: LDS broadcast reads
+        const EvalOut o = eval_pod_node<NSC, false>(cfg, pod, r);
+        if (lane > jj && lane < np) skey[s * kSlotKeyStride + lane] = o.reasons == 0 ? (uint32_t)(o.total + 1) : 0u;
+        ++handled;
+        if (lane == 0) __hip_atomic_store(&heval[me], handled, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
+      }
     }
     return;
   }
   int32_t hn = 0;     // descriptors issued
   uint64_t hown = 0;  // slots whose rows wave 0 built itself
-  // wave 0: every row of `need` is built (wave 1's ready mask or its own)
+  // wave 0: every row of `need` is built (the helpers' ready mask or its own)
   auto wait_rows = [&](uint64_t need) {
     if ((hown & need) == need) return;
     for (;;) {
@@ -328,12 +332,19 @@ __global__ __launch_bounds__(commit_threads(0)) void commit_fq_kernel(CommitArgs
       __builtin_amdgcn_s_sleep(1);
     }
   };
-  // wave 0 (KEYS): the evaluator has taken every descriptor issued so far
+  // wave 0 (KEYS): each helper has evaluated its share of the descriptors issued so far, wave 1 the even entries and
+  // wave 2 the odd ones (called only inside the pod loop, before `hdone`: both still evaluate what they take)
   auto wait_keys = [&]() {
-    while (__builtin_amdgcn_readfirstlane(__hip_atomic_load(heval, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP)) < hn)
+    for (;;) {
+      const uint64_t e = readlane64(
+          __hip_atomic_load(reinterpret_cast<unsigned long long*>(heval), __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP), 0);
+      if ((int32_t)(uint32_t)e >= ((hn + 1) >> 1) && (int32_t)(e >> 32) >= (hn >> 1)) break;
       __builtin_amdgcn_s_sleep(1);
+    }
   };
-  // wave 0 (KEYS): the descriptor of a row it built or changed itself (the row's LDS writes come first: release)
+  // wave 0 (KEYS): the descriptor of a row it built or changed itself (the row's LDS writes come first: release).
+  // The release store waits for those writes to retire; publishing without that wait would rest on another wave
+  // seeing one wave's DS writes in issue order, which the kernel guides do not state, so it stays.
   auto issue_built = [&](int32_t node, int32_t s, int32_t j) {
     if (lane == 0) {
       hdesc[hn] = make_int2(node, s | (j << 8) | (1 << 17));
@@ -422,7 +433,7 @@ __global__ __launch_bounds__(commit_threads(0)) void commit_fq_kernel(CommitArgs
       int32_t node;
       if (cj.fast) {
         // the snapshot-best node is untouched: commits only lower keys, so it wins; no slot holds it, and its row was
-        // prefetched at pass start: wave 1 builds the slot
+        // prefetched at pass start: a helper wave builds the slot
         best = cj.umax;
         ++fast;
         KS_FSTAMP(2);
@@ -440,7 +451,7 @@ __global__ __launch_bounds__(commit_threads(0)) void commit_fq_kernel(CommitArgs
         uint64_t key_mod = 0;
         if (KEYS) {
           wait_keys();
-          KS_FSTAMP(6);  // (diagnostic builds: the slow path's wait, here for the evaluator)
+          KS_FSTAMP(6);  // (diagnostic builds: the slow path's wait, here for the helpers' keys)
           if (lane < nslots) {
             const uint32_t v = skey[lane * kSlotKeyStride + j];
             if (v) key_mod = ((uint64_t)v << 32) | (uint64_t)(0xFFFFFFFFu - (uint32_t)snode);  // gkey(v - 1, snode)
@@ -493,7 +504,7 @@ __global__ __launch_bounds__(commit_threads(0)) void commit_fq_kernel(CommitArgs
           if (lane == s) snode = node;
           if (lane == 0) atomicOr(&touched[node >> 6], 1ull << (node & 63));
           if (node == __builtin_amdgcn_readfirstlane(second_next)) {
-            // its row was prefetched at pass start: wave 1 builds the slot
+            // its row was prefetched at pass start: a helper wave builds the slot
             if (lane == 0) {
               hdesc[hn] = make_int2(node, s | (j << 8) | (1 << 16));
               __hip_atomic_store(hpend, hn + 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
@@ -596,7 +607,7 @@ struct FqLaunch {
   hipError_t (*commit)(bool keys, size_t smem, hipStream_t s, const CommitArgs& a);
   hipError_t (*commit_attr)(bool keys, size_t smem);
 };
-// (keys: the variant with the slot-key table and the evaluator wave; smem includes the table then)
+// (keys: the variant with the slot-key table and the evaluating helper waves; smem includes the table then)
 FqLaunch fq_launch_n0();
 FqLaunch fq_launch_n2();
 FqLaunch fq_launch_n4();
