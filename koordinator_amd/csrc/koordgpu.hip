@@ -2235,8 +2235,8 @@ static int dev_encode(ks_ctx* ctx, const ks_device_cols* dc, int64_t rows, size_
     for (int64_t n = 0; n < rows; ++n) {
       flags[n] = dc->flags ? dc->flags[n] : 0;
       if (flags[n] & KS_DEV_UNMODELLED)
-        KS_FAIL(ctx, KS_EUNSUPPORTED, "node row %lld: preemptible device capacity or device-holding reservations "
-                                      "(device_cache.go:314, deviceshare/reservation.go) are not modelled", (long long)n);
+        KS_FAIL(ctx, KS_EUNSUPPORTED, "node row %lld: KS_DEV_UNMODELLED: FPGA or VF-allocated devices and preemptible device "
+                                      "capacity (device_cache.go:314) are not modelled", (long long)n);
       if (flags[n] & ~(uint32_t)KS_DEV_PRESENT) KS_FAIL(ctx, KS_EINVAL, "node row %lld: device flags 0x%x", (long long)n, flags[n]);
     }
   }

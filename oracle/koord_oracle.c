@@ -1271,6 +1271,9 @@ static int64_t rsv_score(const ko_rsv *rv, const ko_pod *p, int32_t r) {
 static int rsv_dev_candidate(const ko_sched *s, const ko_pod *p, int64_t n, int32_t r, int64_t *ds_score);
 static int rsv_dev_pod(const ko_sched *s, const ko_pod *p);
 
+/* DefaultReservationNormalizeScore(MaxReservationScore = 100, reverse = false): 100 * s / max when max > 0 */
+static int64_t rsv_ds_norm(int64_t ds, int64_t dmax) { return dmax > 0 ? 100 * ds / dmax : ds; }
+
 /* NominateReservation (nominator.go:134-192): FilterReservation survivors, lowest order label
  * first (findMostPreferredReservationByOrder), else the highest scoreReservation (ties: table
  * order).  Also returns the node's preferred order over every matched reservation (PreScore :65). */
@@ -1314,7 +1317,7 @@ static int32_t rsv_nominate(const ko_sched *s, const ko_pod *p, int64_t n, const
   int32_t by_score = -1;
   int64_t bs = -1;
   for (int i = 0; i < ns; i++) {
-    const int64_t t = rsc[i] + (dmax > 0 ? 100 * dsc[i] / dmax : dsc[i]);
+    const int64_t t = rsc[i] + rsv_ds_norm(dsc[i], dmax);
     if (t > bs) {
       bs = t;
       by_score = surv[i];
@@ -1915,18 +1918,24 @@ static int64_t drs_score(const ko_sched *s, int64_t n, const ko_devreq *g, const
 /* DeviceShare's FilterReservation + ScoreReservation for reservation r (plugin.go:322-358, scoring.go:99-142):
  * the reservation holds devices and tryAllocateFromReservation([r], required) allocates; ds_score = its
  * scoreWithReservation.  Returns 1 when r passes. */
-static int rsv_dev_candidate(const ko_sched *s, const ko_pod *p, int64_t n, int32_t r, int64_t *ds_score) {
+static int rsv_dev_candidate_pre(const ko_sched *s, const ko_pod *p, int64_t n, int32_t r, const int64_t *node_pre,
+                                 int64_t *ds_score) {
   *ds_score = 0;
   if (!s->rv.dheld[r] || !s->dv.loaded || !(s->dv.flags[n] & KS_DEV_PRESENT)) return 0;
   ko_drs d;
   drs_build(s, p, n, &d);
   if (!d.on) return 0;
+  /* state.preemptibleDevices[node] (test hook only): appendAllocated(nil, mergedUnmatchedUsed, preemptibleDevices) */
+  for (int w = 0; node_pre && w < KS_DEV_WORDS; w++) d.uu[w] += node_pre[w];
   ko_devreq g;
   if (dev_prepare(s, p, n, &g)) return 0;
   uint32_t out[2];
   if (drs_try(s, p, n, &g, &d, r, KO_ALLOW_ALL, 0, out)) return 0;
   *ds_score = drs_score_rsv(s, n, &g, &d, r, KO_ALLOW_ALL);
   return 1;
+}
+static int rsv_dev_candidate(const ko_sched *s, const ko_pod *p, int64_t n, int32_t r, int64_t *ds_score) {
+  return rsv_dev_candidate_pre(s, p, n, r, NULL, ds_score);
 }
 
 /* DeviceShare Score of a feasible node once the nomination is known (eval_node) */
@@ -3773,4 +3782,39 @@ int ko_test_try_reservation(ko_sched *s, const ks_pod_cols *pc, int64_t node, co
   for (int32_t i = 0; i < m; i++)
     if (drs_try(s, &p, node, &g, &d, rows[i], KO_ALLOW_ALL, 0, out) == 0) return 1;
   return required ? -1 : 0;
+}
+
+/* DeviceShare's FilterReservation + ScoreReservation (rsv_dev_candidate) of pod 0 of pc on `node` for each of the
+ * reservation rows rows[0..m), pinned by scoring_test.go TestScoreReservation and plugin_test.go
+ * Test_Plugin_FilterReservation (tests/golden/deviceshare_reservation_plugin.json): pass[i] = FilterReservation's
+ * verdict, raw[i] = ScoreReservation's value, norm[i] = the value rsv_nominate adds after NormalizeReservationScore over
+ * the passing rows given.  pre (NULL = none, [KS_DEV_WORDS]) is state.preemptibleDevices[node] as the reference's tests
+ * set it.  *node_reason (NULL = not wanted) gets the KS_R_* of DeviceShare's Filter on the node with the same
+ * preemptible vector (0 = feasible).  Returns 0, -2 for a bad node or row. */
+int ko_test_rsv_candidate(ko_sched *s, const ks_pod_cols *pc, int64_t node, const int32_t *rows, int32_t m,
+                          const int64_t *pre, int32_t *pass, int64_t *raw, int64_t *norm, uint32_t *node_reason) {
+  if (node < 0 || node >= s->n) return -2;
+  ko_pod p;
+  load_pod(s, pc, 0, &p);
+  int64_t dmax = 0;
+  for (int32_t i = 0; i < m; i++) {
+    if (rows[i] < 0 || rows[i] >= s->rv.nr) return -2;
+    pass[i] = rsv_dev_candidate_pre(s, &p, node, rows[i], pre, &raw[i]);
+    if (pass[i] && raw[i] > dmax) dmax = raw[i];
+  }
+  for (int32_t i = 0; i < m; i++) norm[i] = pass[i] ? rsv_ds_norm(raw[i], dmax) : 0;
+  if (node_reason) {
+    ko_devreq g;
+    *node_reason = dev_prepare(s, &p, node, &g);
+    if (!*node_reason) {
+      ko_drs d;
+      drs_build(s, &p, node, &d);
+      if (pre) {
+        d.on = 1; /* a preemptible vector alone reaches calcFreeWithPreemptible too (plugin.go:293) */
+        for (int w = 0; w < KS_DEV_WORDS; w++) d.uu[w] += pre[w];
+      }
+      *node_reason = drs_filter(s, &p, node, &g, &d, KO_ALLOW_ALL);
+    }
+  }
+  return 0;
 }
