@@ -33,6 +33,7 @@
 
 #include "ks_pass.h"
 #include "ks_mono.h"
+#include "ks_plan.h"
 #include "ks_fq.h"
 #include "ks_debug.h"
 #include "ks_topo.h"
@@ -1091,6 +1092,7 @@ struct ks_ctx {
   void* numa_blob = nullptr;
   DevNuma nv{};
   int32_t k_cfg = 32;        // the configured candidates per pod (k: what the commit layout leaves of it, commit_attr_set)
+  CommitPlan plan;           // the commit kernel's variant and LDS image (ks_plan.h): set by commit_attr_set, then only read
   int numa_w = kNumaDev;     // NUMA width of the table and of the kernels (ks_numa.h): kNumaWide once a policy node has
                              // more than kNumaDev NUMA nodes (numa_install)
   DevNuma* dnv = nullptr;    // device copy (always allocated: kernels take its address)
@@ -3181,7 +3183,7 @@ int ks_refresh_quota_runtime(ks_ctx* ctx, const ks_quota_tree* t, int32_t nq, in
   qa.total = d64 + 6 * tbl;
   // one wave per dimension; as many dimensions per launch as LDS holds (3 x int64 per quota)
   const size_t per_dim = (size_t)nq * 3 * 8;
-  int dims_per = (int)std::min<size_t>(D, (160 * 1024) / per_dim);
+  int dims_per = (int)std::min<size_t>(D, kLdsBytes / per_dim);
   if (dims_per < 1) {
     (void)hipFree(dbuf);
     KS_FAIL(ctx, KS_EUNSUPPORTED, "quota tree too large for the runtime kernel's LDS (%d quotas)", nq);
@@ -3570,108 +3572,26 @@ static hipEvent_t take_event(ks_ctx* ctx, size_t i) {
   return ctx->ev_pool[i];
 }
 
-static size_t dev_cache_bytes(const ks_ctx* ctx);
-static int kernel_feat(const ks_ctx* ctx);
-// the context's commit variant runs the helper waves (NUMA policies + DeviceShare compiled in, ks_pass.h)
-static bool commit_hint_variant(const ks_ctx* ctx) { return (kernel_feat(ctx) & 12) == 12; }
-static size_t numa_cache_bytes(const ks_ctx* ctx) {
-  return ctx->kc.numa_pol ? (size_t)kMaxBatch * (6 * ctx->numa_w + 1) * 8 : 0;  // NumaSlotT<numa_w>::kWords per slot
-}
-
-// Quota rows are cached in LDS for the pass when the table is small enough and the LDS image fits.
-static int kernel_feat(const ks_ctx* ctx);
-
-static bool commit_qcache(const ks_ctx* ctx) {
-  if (!(ctx->kc.quota_enable && ctx->q.q > 0 && ctx->q.q <= kQuotaLdsRows)) return false;
-  return commit_layout(ctx->k, ctx->nchunks, true, 0, dev_cache_bytes(ctx), numa_cache_bytes(ctx), ctx->q.q, kernel_feat(ctx) == 0,
-                       commit_hint_variant(ctx)).total <= 160 * 1024;
-}
-
-// Kernel variant (FEAT bits, ks_pass.h): 1 Reservation, 2 NodeNUMAResource, 4 the normalized plugins (DeviceShare,
-// TaintToleration / NodeAffinity / NodePorts), 8 NUMA topology policies (with 2), 16 reservations holding devices (with
-// 1 and 4: DeviceShare's restore state, ks_rsv.h; without it the restore code costs the 7 / 15 kernels ~30 % at c3r,
-// though no node runs it).  A context runs the smallest built
-// variant whose bits cover the plugins it enables: a bit that is compiled in but unused still costs registers -- the
-// variants with Reservation and the normalized plugins together spill 180-320 B/lane in the commit kernel, those
-// without Reservation (4, 6, 14) none (hipcc -Rpass-analysis=kernel-resource-usage).
-constexpr int kBuiltFeats[] = {0, 1, 3, 4, 6, 7, 11, 14, 15, 23, 31};  // ascending (koordinator_amd/csrc/Makefile FEATS)
-
-static int kernel_feat(const ks_ctx* ctx) {
-  const int need = (ctx->kc.rsv ? 1 : 0) | (ctx->kc.numa ? 2 : 0) | ((ctx->kc.dev || ctx->kc.stat) ? 4 : 0) |
-                   (ctx->kc.numa_pol ? 10 : 0) | ((ctx->kc.rsv && ctx->kc.dev && ctx->dev_held_any) ? 21 : 0);
-  for (int f : kBuiltFeats)
-    if ((f & need) == need) return f;
-  return 31;
-}
-
-// the slot device region of the commit kernel: GPU state (DeviceShare), then the TaintToleration / NodeAffinity words
-// and NodePorts words (4 x u64 per slot, the region's last kMaxBatch * 32 B) after the pass's PodStat records and the
-// normalization maxima table (ks_pass.h commit_kernel)
-static size_t dev_cache_bytes_with(const ks_ctx* ctx, bool stat_lds) {
-  return (ctx->kc.dev ? (size_t)kDevLdsStride * (kDevTW + kDevQW) * 8 + (size_t)kMaxBatch * 4 : 0) +
-         ((ctx->kc.dev || ctx->kc.stat) ? (size_t)kNormRows * kMaxBatch * 8 : 0) +
-         (ctx->kc.stat ? (size_t)kMaxBatch * 32 : 0) + (stat_lds ? (size_t)kMaxBatch * sizeof(PodStat) : 0);
-}
-
-// The pass's PodStat records go to LDS when the commit image still fits with them (before the quota-row and
-// reservation caches are sized); otherwise the commit reads them from HBM (CommitArgs.stat_lds)
-static bool commit_stat_lds(const ks_ctx* ctx) {
-  if (!ctx->kc.stat) return false;
-  return commit_layout(ctx->k, ctx->nchunks, false, 0, dev_cache_bytes_with(ctx, true), numa_cache_bytes(ctx), ctx->q.q,
-                       kernel_feat(ctx) == 0, commit_hint_variant(ctx)).total + 64 <= 160 * 1024;
-}
-
-static size_t dev_cache_bytes(const ks_ctx* ctx) { return dev_cache_bytes_with(ctx, commit_stat_lds(ctx)); }
-
-static size_t rsv_cache_bytes(const ks_ctx* ctx, int32_t rcap) {
-  return (size_t)kMaxBatch * rcap * 8 * (size_t)(3 + 2 * (3 + ctx->nsc) + 2);  // sizeof(RsvRec<3+nsc>)
-}
-
-// Reservations cached per commit slot: as many as fit next to the rest of the commit layout (<= 8);
-// the quota-row cache yields to it when both do not fit.
-static int32_t commit_rcap(const ks_ctx* ctx, bool* qcache) {
-  *qcache = commit_qcache(ctx);
-  if (!ctx->kc.rsv) return 0;
-  auto fit = [&](bool qc) {
-    const size_t base = commit_layout(ctx->k, ctx->nchunks, qc, 0, dev_cache_bytes(ctx), numa_cache_bytes(ctx), ctx->q.q,
-                                      kernel_feat(ctx) == 0, commit_hint_variant(ctx)).total + 64;
-    const size_t avail = base < 160 * 1024 ? 160 * 1024 - base : 0;
-    return (int32_t)std::min<size_t>(8, avail / rsv_cache_bytes(ctx, 1));
-  };
-  int32_t r = fit(*qcache);
-  if (*qcache && r < 4) {
-    *qcache = false;
-    r = fit(false);
-  }
-  return r;
-}
+// the kernel variant the context's plugins select (ks_plan.h), for the paths that run without a commit plan
+static int kernel_feat(const ks_ctx* ctx) { return plan_feat(ctx->kc, ctx->dev_held_any); }
 
 // the launch wrappers of the FEAT variant (ks_variant.hip)
 // wide: the context's NUMA width is kNumaWide (only the NUMA topology policy plugin sets have such kernels)
 static PassLaunch pass_launcher(int feat, int nsc, bool wide) {
-#define KS_PICK(F) return nsc == 0 ? pass_launch_f##F##_n0_w8() : (nsc == 2 ? pass_launch_f##F##_n2_w8() : pass_launch_f##F##_n4_w8())
+#define KS_PICK(F, W) return nsc == 0 ? pass_launch_f##F##_n0##W() : (nsc == 2 ? pass_launch_f##F##_n2##W() : pass_launch_f##F##_n4##W())
+#define KS_CASE_WIDE(F) case F: KS_PICK(F, _w8);
+#define KS_CASE(F) case F: KS_PICK(F, );
   if (wide)
     switch (feat) {
-      case 15: KS_PICK(15);
-      case 14: KS_PICK(14);
-      case 11: KS_PICK(11);
+      KS_WIDE_FEAT_LIST(KS_CASE_WIDE)
       default: break;
     }
-#undef KS_PICK
-#define KS_PICK(F) return nsc == 0 ? pass_launch_f##F##_n0() : (nsc == 2 ? pass_launch_f##F##_n2() : pass_launch_f##F##_n4())
   switch (feat) {
-    case 31: KS_PICK(31);
-    case 23: KS_PICK(23);
-    case 15: KS_PICK(15);
-    case 14: KS_PICK(14);
-    case 11: KS_PICK(11);
-    case 7: KS_PICK(7);
-    case 6: KS_PICK(6);
-    case 4: KS_PICK(4);
-    case 3: KS_PICK(3);
-    case 1: KS_PICK(1);
-    default: KS_PICK(0);
+    KS_FEAT_LIST(KS_CASE)
+    default: KS_PICK(0, );
   }
+#undef KS_CASE
+#undef KS_CASE_WIDE
 #undef KS_PICK
 }
 
@@ -3689,7 +3609,8 @@ static CandSet cand_set(const ks_ctx* ctx, int i) {
                  ctx->cand_count + r, ctx->cand_total + r};
 }
 
-static CommitArgs commit_args(ks_ctx* ctx, PodStage& st, int32_t total, int32_t batch, bool* qcache, size_t* smem) {
+static CommitArgs commit_args(ks_ctx* ctx, PodStage& st, int32_t total, int32_t batch) {
+  const CommitPlan& plan = ctx->plan;
   CommitArgs ca;
   ca.dn = ctx->dnodes;
   ca.rv = ctx->drv;
@@ -3713,10 +3634,10 @@ static CommitArgs commit_args(ks_ctx* ctx, PodStage& st, int32_t total, int32_t 
   ca.batch = batch;
   ca.k = ctx->k;
   ca.rowcols = ctx->rowcols;
-  ca.rcap = commit_rcap(ctx, qcache);
-  ca.rsv_bytes = (int32_t)rsv_cache_bytes(ctx, ca.rcap);
-  ca.dev_bytes = (int32_t)dev_cache_bytes(ctx);
-  ca.stat_lds = commit_stat_lds(ctx) ? 1 : 0;
+  ca.rcap = plan.rcap;
+  ca.rsv_bytes = (int32_t)plan.rsv_bytes;
+  ca.dev_bytes = (int32_t)plan.dev_bytes;
+  ca.stat_lds = plan.stat_lds ? 1 : 0;
   ca.dv = ctx->ddv;
   ca.dev_M = ctx->dev_M;
   ca.cpuset_list = ctx->cpuset_list;
@@ -3724,7 +3645,7 @@ static CommitArgs commit_args(ks_ctx* ctx, PodStage& st, int32_t total, int32_t 
   ca.cpuset_split = ctx->cpuset_split;
   ca.numa_alloc = ctx->numa_alloc;
   ca.force = 0;
-  ca.numa_bytes = (int32_t)numa_cache_bytes(ctx);
+  ca.numa_bytes = (int32_t)plan.numa_bytes;
   ca.nv = ctx->dnv;
   ca.pipe_base = nullptr;
   ca.carry = nullptr;
@@ -3739,91 +3660,45 @@ static CommitArgs commit_args(ks_ctx* ctx, PodStage& st, int32_t total, int32_t 
   ca.topo_count = ctx->topo_count;
   ca.topo_npad = ctx->npad;
   ca.topo_best = ctx->topo_scr ? &ctx->topo_scr->best_total : nullptr;
-  *smem = commit_layout(ctx->k, ctx->nchunks, *qcache, (size_t)ca.rsv_bytes, (size_t)ca.dev_bytes, (size_t)ca.numa_bytes,
-                        ctx->q.q, kernel_feat(ctx) == 0, commit_hint_variant(ctx)).total;
   return ca;
-}
-
-// The monotone commit kernel (ks_mono.h) runs the passes of a plugin set without Reservation, NodeNUMAResource or
-// DeviceShare whose keys commits can only lower (Fit LeastAllocated + LoadAware) when its LDS fits.  With
-// ElasticQuota the general kernel's pass runs instead (as ks_fq.h's dedicated kernel when the quota tables fit the
-// LDS, fq_commit below): its admission look-ahead for pod j + 1 overlaps pod j's Reserve,
-// and that measured faster than the mono kernel's prebuilt rows at C2 (MI355X, commit 20.6 vs 21.4 ms/step;
-// C5 without quota: mono 275.6 vs general 281.3 ms per 200k pods, profiles/r02_commit_ab.txt).
-// KS_COMMIT_GENERAL=1 keeps the general kernel, =2 forces the mono kernel with quota too (A/B).  ks_assume always
-// uses the general kernel.
-static bool mono_commit(const ks_ctx* ctx, bool qcache, size_t* smem) {
-  static const int64_t mode = env_i64("KS_COMMIT_GENERAL", 0, 0, 2);
-  if (mode == 1 || kernel_feat(ctx) != 0 || !ctx->kc.monotone || ctx->kc.fit_most) return false;
-  if (mode == 0 && ctx->kc.quota_enable) return false;
-  *smem = mono_layout(ctx->k, ctx->nchunks, qcache, ctx->q.q).total;
-  return *smem <= 160 * 1024;
-}
-
-// The dedicated commit kernel of the monotone Fit (LeastAllocated) + LoadAware + ElasticQuota plugin set (ks_fq.h)
-// runs exactly where commit_kernel<NSC, true, 0> would run for a monotone profile: quota tables in LDS, no
-// Reservation / NUMA / DeviceShare / dictionary plugins, not the patched pipeline (its lists can hold emptied
-// chunks and its tops are rebuilt).  KS_COMMIT_FQ=0, read when the context is created, keeps the general kernel
-// (A/B, tests).  Same CommitArgs and LDS layout as the general kernel.
-static bool fq_commit(const ks_ctx* ctx, bool qcache, bool patch) {
-  return ctx->commit_fq && qcache && !patch && kernel_feat(ctx) == 0 && ctx->kc.monotone && !ctx->kc.fit_most &&
-         ctx->kc.quota_enable;
-}
-
-// The dedicated kernel's slot-key table (ks_fq.h, KEYS = true): a slow pod's keys on the touched slots come from the
-// evaluator wave's LDS table instead of wave 0's own lane = slot evaluation.  On when the commit image still fits the
-// CU's LDS with the table (C2: candidates = 32; not with candidates = 64); otherwise, and with KS_FQ_KEYS=0 (read
-// when the context is created: A/B, tests), wave 0 evaluates as before.  *smem: the image with the table.
-static bool fq_keys(const ks_ctx* ctx, bool qcache, bool patch, size_t* smem) {
-  if (!ctx->fq_keys || !fq_commit(ctx, qcache, patch)) return false;
-  const size_t t = commit_layout(ctx->k, ctx->nchunks, true, 0, dev_cache_bytes(ctx), numa_cache_bytes(ctx), ctx->q.q, true,
-                                 false, true).total;
-  if (t > 160 * 1024) return false;
-  *smem = t;
-  return true;
 }
 
 static FqLaunch fq_launcher(int nsc) { return nsc == 0 ? fq_launch_n0() : (nsc == 2 ? fq_launch_n2() : fq_launch_n4()); }
 
-// Reserve's NodeNUMAResource / DeviceShare allocations ahead of the commit (reserve_pre_kernel): on for
-// the NUMA topology policy variants when policy nodes are loaded; KS_PRE_RSV=0 turns it off (A/B).
-static bool pre_reserve(const ks_ctx* ctx) {
-  static const int64_t env_pre = env_i64("KS_PRE_RSV", 1, 0, 1);
-  return env_pre != 0 && ctx->kc.numa_pol;
-}
-
-// the commit kernel's LDS size for this context: checked against the CU's 160 KB and set on the variant
+// The commit plan of this context (ks_plan.h): computed here at every entry point that commits, so that it never
+// outlives a table reload; checked against the CU's LDS, and its image sizes set on the kernels it selects.
 static int commit_attr_set(ks_ctx* ctx) {
-  // (unreachable: the loads refuse the combination, dev_apply_held / numa_install)
-  if (ctx->numa_w == kNumaWide && kernel_feat(ctx) == 31)
+  static const int64_t env_general = env_i64("KS_COMMIT_GENERAL", 0, 0, 2);
+  static const int64_t env_pre = env_i64("KS_PRE_RSV", 1, 0, 1);
+  CommitPlanIn in{};
+  in.kc = ctx->kc;
+  in.k_cfg = ctx->k_cfg;
+  in.nchunks = ctx->nchunks;
+  in.nsc = ctx->nsc;
+  in.numa_w = ctx->numa_w;
+  in.q = ctx->q.q;
+  in.dev_held_any = ctx->dev_held_any;
+  in.commit_fq = ctx->commit_fq;
+  in.fq_keys = ctx->fq_keys;
+  in.general_mode = (int)env_general;
+  in.pre_rsv = env_pre != 0;
+  const CommitPlan& plan = ctx->plan = commit_plan(in);
+  if (plan.status == PlanStatus::kHeldWide)
     KS_FAIL(ctx, KS_EUNSUPPORTED,
             "reservations holding devices together with a NUMA-policy node with more than %d NUMA nodes", kNumaDev);
-  // A NUMA table at width 8 doubles the slots' NUMA cache (25 KB); next to DeviceShare's slot cache the layout then
-  // exceeds the LDS at the default 32 candidates per pod.  Such a context keeps fewer candidates per pod: the
-  // placements do not depend on the list length (a pod whose list runs out cuts the pass), only the pass count does.
-  ctx->k = ctx->k_cfg;
-  while (ctx->numa_w == kNumaWide && ctx->k > 8 &&
-         commit_layout(ctx->k, ctx->nchunks, false, 0, dev_cache_bytes(ctx), numa_cache_bytes(ctx), ctx->q.q,
-                       kernel_feat(ctx) == 0, commit_hint_variant(ctx)).total + 64 > 160 * 1024)
-    ctx->k -= 8;
-  bool qcache = false;
-  const int32_t rcap = commit_rcap(ctx, &qcache);
-  const size_t smem = commit_layout(ctx->k, ctx->nchunks, qcache, rsv_cache_bytes(ctx, rcap), dev_cache_bytes(ctx),
-                                    numa_cache_bytes(ctx), ctx->q.q, kernel_feat(ctx) == 0, commit_hint_variant(ctx)).total;
-  if (smem > 160 * 1024)
-    KS_FAIL(ctx, KS_EUNSUPPORTED, "too many nodes for the commit kernel's LDS (%lld nodes, %zu B)", (long long)ctx->n, smem);
-  hipError_t e = pass_launcher(kernel_feat(ctx), ctx->nsc, ctx->numa_w == kNumaWide).commit_attr(qcache, smem);
-  if (e != hipSuccess) KS_FAIL(ctx, KS_EHIP, "hipFuncSetAttribute(commit LDS %zu): %s", smem, hipGetErrorString(e));
-  if (fq_commit(ctx, qcache, false)) {
-    size_t fsmem = smem;
-    const bool keys = fq_keys(ctx, qcache, false, &fsmem);
-    e = fq_launcher(ctx->nsc).commit_attr(keys, fsmem);
-    if (e != hipSuccess) KS_FAIL(ctx, KS_EHIP, "hipFuncSetAttribute(fq commit LDS %zu): %s", fsmem, hipGetErrorString(e));
+  ctx->k = plan.k;
+  if (plan.status == PlanStatus::kTooLarge)
+    KS_FAIL(ctx, KS_EUNSUPPORTED, "too many nodes for the commit kernel's LDS (%lld nodes, %zu B)", (long long)ctx->n, plan.smem);
+  hipError_t e = pass_launcher(plan.feat, ctx->nsc, plan.wide).commit_attr(plan.qcache, plan.smem);
+  if (e != hipSuccess) KS_FAIL(ctx, KS_EHIP, "hipFuncSetAttribute(commit LDS %zu): %s", plan.smem, hipGetErrorString(e));
+  if (plan.fq) {
+    e = fq_launcher(ctx->nsc).commit_attr(plan.fq_keys, plan.fq_smem);
+    if (e != hipSuccess) KS_FAIL(ctx, KS_EHIP, "hipFuncSetAttribute(fq commit LDS %zu): %s", plan.fq_smem, hipGetErrorString(e));
   }
-  size_t msmem = 0;
-  if (mono_commit(ctx, qcache, &msmem)) {
-    e = pass_launcher(0, ctx->nsc, false).commit_mono_attr(qcache, msmem);
-    if (e != hipSuccess) KS_FAIL(ctx, KS_EHIP, "hipFuncSetAttribute(mono commit LDS %zu): %s", msmem, hipGetErrorString(e));
+  if (plan.mono) {
+    e = pass_launcher(0, ctx->nsc, false).commit_mono_attr(plan.qcache, plan.mono_smem);
+    if (e != hipSuccess)
+      KS_FAIL(ctx, KS_EHIP, "hipFuncSetAttribute(mono commit LDS %zu): %s", plan.mono_smem, hipGetErrorString(e));
   }
   return KS_OK;
 }
@@ -4184,15 +4059,7 @@ static int topo_step(ks_ctx* ctx) {
     return KS_OK;
   }
   HIPCHK(ctx, launch_topo_norm(ctx->stream, ta));
-  bool qcache = false;
-  size_t smem = 0;
-  CommitArgs ca = commit_args(ctx, ctx->st, ctx->np, 1, &qcache, &smem);
-  if (qcache) {
-    // one pod: the quota rows are read from HBM (copying the table into LDS would cost more than the pod's reads)
-    qcache = false;  // (the reservation cache that fit next to the quota rows fits without them)
-    smem = commit_layout(ctx->k, ctx->nchunks, false, (size_t)ca.rsv_bytes, (size_t)ca.dev_bytes, (size_t)ca.numa_bytes,
-                         ctx->q.q, kernel_feat(ctx) == 0, commit_hint_variant(ctx)).total;
-  }
+  CommitArgs ca = commit_args(ctx, ctx->st, ctx->np, 1);
   ca.topo = 2;
   ca.cand_chunk = ctx->topo_cchunk;
   ca.cand_t = ctx->topo_ct;
@@ -4200,7 +4067,9 @@ static int topo_step(ks_ctx* ctx) {
   ca.cand_bound = ctx->topo_cbound;
   ca.cand_top = ctx->topo_ctop;
   ca.cand_second = ctx->topo_csecond;
-  HIPCHK(ctx, pass_launcher(kernel_feat(ctx), ctx->nsc, ctx->numa_w == kNumaWide).commit(qcache, smem, ctx->stream, ca));
+  // one pod: the quota rows are read from HBM (copying the table into LDS would cost more than the pod's reads)
+  const CommitPlan& plan = ctx->plan;
+  HIPCHK(ctx, pass_launcher(plan.feat, ctx->nsc, plan.wide).commit(false, plan.smem_no_qcache, ctx->stream, ca));
   return cores_pass_refresh(ctx);
 }
 
@@ -4399,9 +4268,8 @@ static int launch_pass(ks_ctx* ctx, int32_t ppw, int sweep_blocks, const PipeSha
     HIPCHK(ctx, hipEventRecord(ctx->pev_sel[k % kPipeEvents], ss));
     HIPCHK(ctx, hipStreamWaitEvent(cs, ctx->pev_sel[k % kPipeEvents], 0));
   }
-  bool qcache = false;
-  size_t smem = 0;
-  CommitArgs ca = commit_args(ctx, ctx->st, ctx->np, ctx->batch, &qcache, &smem);
+  const CommitPlan& plan = ctx->plan;
+  CommitArgs ca = commit_args(ctx, ctx->st, ctx->np, ctx->batch);
   if (pipe) {
     ca.pipe_base = base;
     ca.carry = carry;
@@ -4418,18 +4286,13 @@ static int launch_pass(ks_ctx* ctx, int32_t ppw, int sweep_blocks, const PipeSha
     ca.cand_top = (const uint64_t*)(ctx->pipe_top + (size_t)(k & 1) * kMaxBatch);  // rebuilt by the list re-evaluation
     ca.top_reset = ctx->pipe_top + (size_t)(k & 1) * kMaxBatch;
   }
-  size_t msmem = 0;
-  const bool mono = mono_commit(ctx, qcache, &msmem);
-  if (!mono && !pipe && pl.reserve_pre && pre_reserve(ctx)) ca.pre_rsv = ctx->pre_rsv;
+  if (!plan.mono && !pipe && pl.reserve_pre && plan.pre_reserve) ca.pre_rsv = ctx->pre_rsv;
   rec(2, cs);
   if (ca.pre_rsv) HIPCHK(ctx, pl.reserve_pre(ctx->batch, cs, ca));  // (timed with the commit)
-  if (mono) HIPCHK(ctx, pl.commit_mono(qcache, msmem, cs, ca));
-  else if (fq_commit(ctx, qcache, patch)) {
-    size_t fsmem = smem;
-    const bool keys = fq_keys(ctx, qcache, patch, &fsmem);
-    HIPCHK(ctx, fq_launcher(ctx->nsc).commit(keys, fsmem, cs, ca));
-  }
-  else HIPCHK(ctx, pl.commit(qcache, smem, cs, ca));
+  // (the dedicated fq kernel does not run the patched pipeline's passes, ks_plan.h)
+  if (plan.mono) HIPCHK(ctx, pl.commit_mono(plan.qcache, plan.mono_smem, cs, ca));
+  else if (plan.fq && !patch) HIPCHK(ctx, fq_launcher(ctx->nsc).commit(plan.fq_keys, plan.fq_smem, cs, ca));
+  else HIPCHK(ctx, pl.commit(plan.qcache, plan.smem, cs, ca));
   rec(2, cs);
   if (pipe) HIPCHK(ctx, hipEventRecord(ctx->pev_com[k % kPipeEvents], cs));
   ctx->pipe_k = k + 1;
@@ -4451,7 +4314,7 @@ static int schedule_staged_impl(ks_ctx* ctx) {
     if (int rc = commit_attr_set(ctx); rc != KS_OK) return rc;
     hipError_t e = hipSuccess;
     const size_t sel_smem = select_smem(ctx->nchunks);
-    if (sel_smem > 160 * 1024) KS_FAIL(ctx, KS_EUNSUPPORTED, "too many nodes for the select kernel's LDS (%lld nodes)", (long long)ctx->n);
+    if (sel_smem > kLdsBytes) KS_FAIL(ctx, KS_EUNSUPPORTED, "too many nodes for the select kernel's LDS (%lld nodes)", (long long)ctx->n);
     e = hipFuncSetAttribute((const void*)select_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sel_smem);
     if (e != hipSuccess) KS_FAIL(ctx, KS_EHIP, "hipFuncSetAttribute(select LDS %zu): %s", sel_smem, hipGetErrorString(e));
     if (ctx->kc.dev && !ctx->kc.rsv && !ctx->kc.stat && ctx->dcache_words < (int64_t)kMaxBatch * ctx->npad) {
@@ -4611,19 +4474,10 @@ static int schedule_staged_impl(ks_ctx* ctx) {
   ctx->stats.bubble_passes = (int64_t)cnt[4];
   ctx->stats.pre_reserves = (int64_t)cnt[5];
   ctx->stats.pipelined = pipe ? (pipe->patch ? 2 : 1) : 0;
-  {
-    bool qc = false;
-    const int32_t rcap = commit_rcap(ctx, &qc);
-    const CommitLayout L = commit_layout(ctx->k, ctx->nchunks, qc, rsv_cache_bytes(ctx, rcap), dev_cache_bytes(ctx),
-                                         numa_cache_bytes(ctx), ctx->q.q, kernel_feat(ctx) == 0, commit_hint_variant(ctx));
-    ctx->stats.commit_lds_bytes = (int64_t)L.total;
-    ctx->stats.commit_helpers = L.hint ? 1 : 0;
-    size_t fsmem = 0, msmem = 0;
-    if (!mono_commit(ctx, qc, &msmem) && fq_keys(ctx, qc, pipe && pipe->patch, &fsmem)) {
-      ctx->stats.commit_lds_bytes = (int64_t)fsmem;
-      ctx->stats.commit_helpers = 2;
-    }
-  }
+  const CommitPlan& plan = ctx->plan;
+  const bool keys = !plan.mono && plan.fq_keys && !(pipe && pipe->patch);
+  ctx->stats.commit_lds_bytes = (int64_t)(keys ? plan.fq_smem : plan.smem);
+  ctx->stats.commit_helpers = keys ? 2 : (plan.hint ? 1 : 0);
   for (int i = 0; i < 8; ++i) ctx->stats.diag[i] = (int64_t)cnt[8 + i];
   for (size_t i = 0; i + 1 < evs.size(); i += 2) {
     float e = 0;
@@ -5230,12 +5084,11 @@ int ks_assume(ks_ctx* ctx, const ks_pod_cols* pod, int32_t node, ks_result* out,
     HIPCHK(ctx, hipMemsetAsync(ctx->cpuset_out, 0, sizeof(CpuSet), ctx->stream));
     HIPCHK(ctx, hipMemsetAsync(ctx->numa_alloc, 0, (size_t)2 * ctx->numa_w * 8, ctx->stream));
   }
-  bool qcache = false;
-  size_t smem = 0;
-  CommitArgs ca = commit_args(ctx, ctx->ast, 1, 1, &qcache, &smem);
+  CommitArgs ca = commit_args(ctx, ctx->ast, 1, 1);
   ca.force = 1;
   if (ca.topo) ca.topo = 3;  // count the pod's properties on the node
-  HIPCHK(ctx, pass_launcher(kernel_feat(ctx), ctx->nsc, ctx->numa_w == kNumaWide).commit(qcache, smem, ctx->stream, ca));
+  const CommitPlan& plan = ctx->plan;
+  HIPCHK(ctx, pass_launcher(plan.feat, ctx->nsc, plan.wide).commit(plan.qcache, plan.smem, ctx->stream, ca));
   if (ctx->cpu_loaded && ctx->n > 0) {
     cpuset_launch(ctx, (const PodRec*)ctx->ast.recs);
     HIPCHK(ctx, hipGetLastError());

@@ -31,6 +31,7 @@ namespace ks {
 constexpr int kWave = 64;
 constexpr int kMaxBatch = 64;  // pods per sweep pass (one lane per pod in the pass result)
 constexpr int kMaxCand = 64;   // candidate chunks per pod
+constexpr size_t kLdsBytes = 160 * 1024;  // the CU's LDS: what one workgroup's dynamic image may take
 
 // internal pod flag: podRequest is all-zero with no scalar keys (fitsRequest early return)
 constexpr uint32_t kPodAllZero = 0x100u;

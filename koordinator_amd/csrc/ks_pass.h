@@ -532,7 +532,7 @@ __host__ __device__ inline CommitLayout commit_layout(int32_t k, int64_t nchunks
   L.help = o;
   // slot-row hand-off to the builder wave (FEAT 0): descriptors, issued count, done flag, ready mask; with both the
   // device and the NUMA slot caches, the helper waves' hints and DeviceShare variants when they still fit the CU's LDS
-  L.hint = hint_ok && dev_bytes && numa_bytes && o + kHelpHintBytes + (size_t)nchunks * 8 <= (size_t)160 * 1024;
+  L.hint = hint_ok && dev_bytes && numa_bytes && o + kHelpHintBytes + (size_t)nchunks * 8 <= kLdsBytes;
   o += L.hint ? kHelpHintBytes : kHelpBytes;
   L.touched = o;
   o += (size_t)nchunks * 8;  // u64 per chunk: lanes touched in this pass
@@ -784,9 +784,9 @@ __global__ __launch_bounds__(commit_threads(FEAT)) void commit_kernel(CommitArgs
   int32_t* sdev_pres = reinterpret_cast<int32_t*>(sdev_use + kDevLdsStride * DU);
   int64_t* snp = reinterpret_cast<int64_t*>(smem_raw + lay.snp);  // [slot][NumaSlotT<NW>::kWords]
   // per slot: the node's dictionary-bit plugin words (taints hard, soft, labels, host ports -- the last one updated
-  // by every Reserve of the pass): the last kMaxBatch * 32 B of the slot device region (dev_cache_bytes)
+  // by every Reserve of the pass): the last kMaxBatch * 32 B of the slot device region (ks_plan.h dev_bytes)
   // and before them the pass's PodStat records (Cfg.stat), and before those the normalization maxima table
-  // ([kNormRows][kMaxBatch], DeviceShare variants): dev_cache_bytes
+  // ([kNormRows][kMaxBatch], DeviceShare variants): ks_plan.h dev_bytes
   // (the PodStat records only with CommitArgs.stat_lds)
   unsigned char* const sdev_end = smem_raw + lay.sdev + a.dev_bytes;
   uint64_t* sstat = reinterpret_cast<uint64_t*>(sdev_end - (size_t)kMaxBatch * 32);
@@ -2165,25 +2165,17 @@ struct PassLaunch {
   // NUMA topology policy variants only (else null): reserve_pre_kernel, one workgroup per pod of the pass
   hipError_t (*reserve_pre)(int blocks, hipStream_t s, const CommitArgs& a);
 };
+// The built FEAT variants, ascending (the Makefile's FEATS builds the same set: a mismatch is a link error), and those
+// built a second time at NUMA width 8 (ks_variant.hip with -DKS_NW=8, the Makefile's WFEATS).  The declarations
+// below, kBuiltFeats (ks_plan.h) and pass_launcher's cases (koordgpu.hip) are generated from these lists.
+#define KS_FEAT_LIST(X) X(0) X(1) X(3) X(4) X(6) X(7) X(11) X(14) X(15) X(23) X(31)
+#define KS_WIDE_FEAT_LIST(X) X(11) X(14) X(15)
 #define KS_DECLARE_VARIANT(F) PassLaunch pass_launch_f##F##_n0(); PassLaunch pass_launch_f##F##_n2(); PassLaunch pass_launch_f##F##_n4();
-KS_DECLARE_VARIANT(0)
-KS_DECLARE_VARIANT(1)
-KS_DECLARE_VARIANT(3)
-KS_DECLARE_VARIANT(4)
-KS_DECLARE_VARIANT(6)
-KS_DECLARE_VARIANT(7)
-KS_DECLARE_VARIANT(11)
-KS_DECLARE_VARIANT(14)
-KS_DECLARE_VARIANT(15)
-KS_DECLARE_VARIANT(23)
-KS_DECLARE_VARIANT(31)
+KS_FEAT_LIST(KS_DECLARE_VARIANT)
 #undef KS_DECLARE_VARIANT
-// the NUMA topology policy plugin sets at NUMA width 8 (ks_variant.hip with -DKS_NW=8)
 #define KS_DECLARE_WIDE(F) \
   PassLaunch pass_launch_f##F##_n0_w8(); PassLaunch pass_launch_f##F##_n2_w8(); PassLaunch pass_launch_f##F##_n4_w8();
-KS_DECLARE_WIDE(11)
-KS_DECLARE_WIDE(14)
-KS_DECLARE_WIDE(15)
+KS_WIDE_FEAT_LIST(KS_DECLARE_WIDE)
 #undef KS_DECLARE_WIDE
 
 }  // namespace ks
