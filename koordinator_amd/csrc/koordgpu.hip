@@ -3480,6 +3480,7 @@ static int validate_pods(ks_ctx* ctx, const ks_pod_cols* pc, int32_t p) {
         KS_FAIL(ctx, KS_EINVAL, "pod %d: preferred node affinity weight %d outside [0, 100]", i, pc->affinity_weight[t][i]);
   const int64_t* cols[] = {pc->req_milli_cpu, pc->req_memory, pc->req_ephemeral, pc->nonzero_milli_cpu,
                            pc->nonzero_memory, pc->la_req_cpu, pc->la_lim_cpu, pc->la_req_memory, pc->la_lim_memory,
+                           pc->la_dflt_cpu, pc->la_dflt_memory,  // the estimate of a pod with no request (a score-term request)
                            pc->gpu_core, pc->gpu_memory, pc->gpu_memory_ratio, pc->rdma};
   for (const int64_t* c : cols)
     if (check_range64(ctx, c, p, "pod quantity") != KS_OK) return KS_EINVAL;

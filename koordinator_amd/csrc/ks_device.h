@@ -253,7 +253,10 @@ __device__ __forceinline__ void term_take(Term& t, int64_t r, double rd) {
 // truncates to itself (x >= x* + B - 2^-45 > x*), and a non-integral one is at least 1/c > 2^-43 below the
 // next integer (c < 2^43), which B + 2^-45 < 2^-43 cannot cross.  For h < p, x* <= -100/c and x < 1, so the
 // result is 0.  tests/test_score_f64.py replays the formula on the boundary cases with exact rational
-// arithmetic.
+// arithmetic; tests/test_gpu_score_edges.py runs the kernels on them (both paths in one wave, capacities on both
+// sides of kBigCap and up to 2^56 - 1, requests on both sides of kBigReq, the Term state after Reserves in every
+// commit kernel) against the int64 formulas.  The bound has slack up to c = 2^43 + small, none at 2^44: the formula
+// is off by one at c = 2^44 - 15, h - p = floor(c / 100).
 __device__ __forceinline__ int32_t term_least(const Term& t, double pd) {
   return (int32_t)fmax(fma(t.hd - pd, t.r, kScoreBias), 0.0);
 }

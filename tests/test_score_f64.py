@@ -3,7 +3,11 @@ exact: trunc(max(fma(100(h-p), fl(1/c), 2^-44), 0)) == floor(100(h-p)/c) (Go's i
 load_aware.go:388-397 / least_allocated.go:45-54) and the MostAllocated counterpart, for every capacity
 c < 2^43 and request below 2^46.  The fma is replayed with exact rational arithmetic (Fraction -> float is
 correctly rounded), so this checks the IEEE result the hardware computes, on the cases the error bound is
-tight for: quotients that are exact integers, and quotients one unit (1/c) below an integer."""
+tight for: quotients that are exact integers, and quotients one unit (1/c) below an integer.
+
+This file replays the formula on the host and never runs a kernel.  tests/test_gpu_score_edges.py backs it on the
+device: the kernels' own fma, bias, path switch (kBigCap / kBigReq) and Term state (term_set, the commit kernels' slot
+rows, term_take after Reserves) on the same kind of boundary cases, against the int64 formulas."""
 from fractions import Fraction
 
 import numpy as np
