@@ -1013,6 +1013,71 @@ int ks_preempt(ks_ctx *ctx, const ks_pod_cols *pod, int32_t priority, uint32_t f
                const uint8_t *unresolvable, ks_preempt_result *out, int32_t *victims, int32_t victims_cap,
                uint8_t *node_status);
 
+/* ---- nominated pods (upstream PodNominator + RunFilterPluginsWithNominatedPods, kube-scheduler v1.24
+ * framework/runtime/framework.go; the reference reaches it through frameworkext/framework_extender.go:204-221).
+ * ks_preempt nominates a node for the preemptor (KS_P_NOMINATED); until that pod is assumed there, the table below is what
+ * keeps the freed room for it.  One row per nominated pod (Status.NominatedNodeName set, not yet assumed).  For pod P on
+ * node X the rows of X with priority >= P's priority and id != P's id count: the Filters run with them added to X's
+ * NodeInfo (Requested, every scalar and the pod count go up) and, if that passes, once more without them; scores are
+ * computed without them over the nodes that remain feasible.  Additive to ABI 11: no existing
+ * struct or ks_abi_layout word changes; the size of ks_nominated_cols travels with the load call. ---- */
+typedef struct ks_nominated_cols {
+  const int32_t *node;          /* node row the pod is nominated to */
+  const int32_t *priority;      /* corev1helpers.PodPriority */
+  const int64_t *id;            /* the caller's key of the pod (e.g. a UID hash), >= 0, unique in the table */
+  const int64_t *req_milli_cpu; /* upstream computePodResourceRequest, as ks_pod_cols (Fit PreFilter); NULL = 0 */
+  const int64_t *req_memory;
+  const int64_t *req_ephemeral;
+  const int64_t *req_scalar[KS_MAX_SCALARS];
+} ks_nominated_cols;
+
+/* whose Filter runs */
+typedef struct ks_nomination {
+  int32_t priority;       /* the pod's priority */
+  int32_t nominated_node; /* the pod's own Status.NominatedNodeName as a node row, -1 = none */
+  int64_t self_id;        /* the pod's id when it has a row in the table itself, -1 = none */
+} ks_nomination;
+
+/* Replaces the whole table (m = 0 clears it); sizeof_cols = sizeof(ks_nominated_cols) of the caller's header.  Call
+ * after ks_load_nodes; ks_load_nodes drops the table (node rows are renumbered).  KS_EINVAL: a node row outside the
+ * loaded nodes, a negative request or id, an id listed twice, another sizeof_cols.  KS_EUNSUPPORTED: a non-empty table
+ * with a plugin whose Filter reads the node's other pods in a way the table does not carry -- NodePorts,
+ * PodTopologySpread / InterPodAffinity, NodeNUMAResource, DeviceShare, Reservation (the set ks_preempt models is Fit,
+ * LoadAware, ElasticQuota, BalancedAllocation, TaintToleration, NodeAffinity; of these only Fit's verdict changes with
+ * the added pods).  While a non-empty table is loaded the entry points that carry no priority -- ks_schedule,
+ * ks_stage_pods, ks_schedule_staged, ks_eval_pod, ks_eval_pod_debug, ks_eval_pod_summary -- answer KS_EUNSUPPORTED
+ * instead of ignoring it; with an empty or absent table every entry point behaves as before.  ks_checkpoint /
+ * ks_restore cover the table. */
+int ks_load_nominated(ks_ctx *ctx, const ks_nominated_cols *cols, int64_t m, size_t sizeof_cols);
+/* Removes the rows with these ids: the nominated pod was assumed (ks_assume) or deleted, or its nomination was cleared
+ * (PodNominator.DeleteNominatedPodIfExists).  An id without a row is ignored. */
+int ks_delete_nominated(ks_ctx *ctx, const int64_t *ids, int64_t m);
+
+/* ks_eval_pod with the nominated table applied: same validation, outputs and reason bits; a node that fails only with
+ * the nominated pods added carries the KS_R_FIT_* bits of that pass, and the normalized scores (TaintToleration,
+ * NodeAffinity) are over the nodes that remain feasible.  Every KS_R_* bit is taken, so this call cannot mark "not the
+ * nominated node": who->nominated_node is validated and otherwise unused here, every node keeps its own reasons and
+ * scores, and the single-node result of a feasible nominated node comes from ks_eval_pod_summary_nominated. */
+int ks_eval_pod_nominated(ks_ctx *ctx, const ks_pod_cols *pod, const ks_nomination *who, uint32_t *reasons,
+                          int64_t *scores, int64_t *total);
+/* ks_eval_pod_summary with the nominated table applied.  When who->nominated_node >= 0 and that node passes the
+ * Filters (nominated pods included), upstream's evaluateNominatedNode makes it the only feasible node: feasible = 1,
+ * best_node and the one top row are that node with its scores normalized over the one-node set, feasible_bits has
+ * its bit alone; reason_nodes, unresolvable and unresolvable_bits still describe every node's own status (no FitError
+ * is built in that case).  Otherwise the summary is the full sweep's. */
+int ks_eval_pod_summary_nominated(ks_ctx *ctx, const ks_pod_cols *pod, const ks_nomination *who,
+                                  uint32_t unresolvable_mask, int32_t top_n, ks_pod_summary *out, int32_t *top_nodes,
+                                  int64_t *top_totals, int64_t *top_scores, uint64_t *feasible_bits,
+                                  uint64_t *unresolvable_bits);
+/* ks_preempt whose dry runs see the nominated table: every Fit check inside SelectVictimsOnNode (after the potential
+ * victims are removed and after each reprieve) runs on Requested and pod count plus the node's nominated rows of
+ * priority >= `priority`, the row with id self_id (the preemptor's own earlier nomination, -1 = none) excluded.  The
+ * quota checks are unchanged (ElasticQuota's AddPod writes a cloned state no Filter reads).  ks_preempt itself, with a
+ * table loaded, is this call with self_id = -1. */
+int ks_preempt_nominated(ks_ctx *ctx, const ks_pod_cols *pod, int32_t priority, uint32_t flags, int32_t nominated_node,
+                         int64_t self_id, const uint8_t *unresolvable, ks_preempt_result *out, int32_t *victims,
+                         int32_t victims_cap, uint8_t *node_status);
+
 int ks_shard_unique_id(uint8_t *out /* KS_SHARD_ID_BYTES */);
 /* Node sharding over nranks processes (one per GPU): this rank sweeps its chunk range as virtual_shards
  * shards; the per-shard candidates are exchanged by one ncclAllGather per pass and the normalization maxima by one

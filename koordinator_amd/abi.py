@@ -527,6 +527,11 @@ EXPORTED_SYMBOLS = [
     "ks_shard_init_loopback",
     "ks_load_node_pods",
     "ks_preempt",
+    "ks_load_nominated",
+    "ks_delete_nominated",
+    "ks_eval_pod_nominated",
+    "ks_eval_pod_summary_nominated",
+    "ks_preempt_nominated",
 ]
 KS_SHARD_ID_BYTES = 128
 
@@ -588,6 +593,28 @@ class KsPodSummary(C.Structure):
         ("best_total", C.c_int64),
         ("best_node", C.c_int32),
         ("top_count", C.c_int32),
+    ]
+
+
+# ---- nominated pods (ks_load_nominated; additive to ABI 11: not part of ks_abi_layout, the size of KsNominatedCols
+# travels with the load call) ----
+class KsNominatedCols(C.Structure):
+    _fields_ = [
+        ("node", P32),
+        ("priority", P32),
+        ("id", P64),
+        ("req_milli_cpu", P64),
+        ("req_memory", P64),
+        ("req_ephemeral", P64),
+        ("req_scalar", P64 * KS_MAX_SCALARS),
+    ]
+
+
+class KsNomination(C.Structure):
+    _fields_ = [
+        ("priority", C.c_int32),
+        ("nominated_node", C.c_int32),
+        ("self_id", C.c_int64),
     ]
 
 

@@ -667,6 +667,54 @@ class NodePodTable:
         return c
 
 
+class NominatedTable:
+    """The nominated pods (ks_nominated_cols): one row per pod with Status.NominatedNodeName set and not yet assumed --
+    the node row it is nominated to, its priority, the caller's unique id (>= 0) and its request vector ([dim][row]:
+    cpu, memory, ephemeral-storage, scalar[k]), as Fit's PreFilter computes it."""
+
+    def __init__(self, m: int):
+        self.m = int(m)
+        self.node = np.zeros(self.m, np.int32)
+        self.priority = np.zeros(self.m, np.int32)
+        self.id = np.arange(self.m, dtype=np.int64)
+        self.req = np.zeros((abi.KS_RSV_DIMS, self.m), np.int64)
+
+    def copy(self) -> "NominatedTable":
+        return self.rows(np.arange(self.m))
+
+    def rows(self, idx) -> "NominatedTable":
+        idx = np.asarray(idx, np.int64)
+        t = NominatedTable(len(idx))
+        for k in ("node", "priority", "id"):
+            setattr(t, k, getattr(self, k)[idx].copy())
+        t.req = self.req[:, idx].copy()
+        return t
+
+    def sums(self, n: int, priority: int, self_id: int = -1):
+        """(req [dim][n], count [n]): per node the rows that count for a pod of `priority` whose own id is self_id
+        (priority >= the pod's, id != its own), summed"""
+        keep = (self.priority >= priority) & (self.id != self_id)
+        req = np.zeros((abi.KS_RSV_DIMS, n), np.int64)
+        for d in range(abi.KS_RSV_DIMS):
+            np.add.at(req[d], self.node[keep], self.req[d][keep])
+        return req, np.bincount(self.node[keep], minlength=n).astype(np.int32)
+
+    def ks(self) -> abi.KsNominatedCols:
+        c = abi.KsNominatedCols()
+        for name, dt in (("node", np.int32), ("priority", np.int32), ("id", np.int64), ("req", np.int64)):
+            setattr(self, name, np.ascontiguousarray(getattr(self, name), dt))
+        c.node = _p32(self.node)
+        c.priority = _p32(self.priority)
+        c.id = _p64(self.id)
+        c.req_milli_cpu = _p64(self.req[0])
+        c.req_memory = _p64(self.req[1])
+        c.req_ephemeral = _p64(self.req[2])
+        for k in range(abi.KS_MAX_SCALARS):
+            c.req_scalar[k] = _p64(self.req[3 + k])
+        c._keep = self
+        return c
+
+
 class NodeState:
     """Host buffers for ks_read_nodes / ko_read_nodes."""
 

@@ -702,16 +702,18 @@ __global__ __launch_bounds__(1024) void dev_normalize_debug_kernel(int64_t n, co
 __global__ __launch_bounds__(1024) void stat_normalize_debug_kernel(int64_t n, const uint32_t* reasons,
                                                                     const int32_t* raw, int64_t* scores,
                                                                     int64_t* total, int64_t w, int32_t slot,
-                                                                    int32_t reverse) {
+                                                                    int32_t reverse, int32_t only) {
   __shared__ int32_t s_max;
   if (threadIdx.x == 0) s_max = 0;
   __syncthreads();
+  // only >= 0: the pod's nominated node, the whole feasible set when it is feasible (evaluateNominatedNode)
+  const bool one = only >= 0 && reasons[only] == 0;
   for (int64_t i = threadIdx.x; i < n; i += blockDim.x)
-    if (!reasons[i]) atomicMax(&s_max, raw[i]);
+    if (!reasons[i] && (!one || i == only)) atomicMax(&s_max, raw[i]);
   __syncthreads();
   const int64_t mx = s_max;
   for (int64_t i = threadIdx.x; i < n; i += blockDim.x) {
-    if (reasons[i]) continue;
+    if (reasons[i] || (one && i != only)) continue;
     int64_t sc;
     if (mx == 0) sc = reverse ? 100 : raw[i];
     else sc = reverse ? 100 - 100 * (int64_t)raw[i] / mx : 100 * (int64_t)raw[i] / mx;
@@ -1140,6 +1142,17 @@ struct ks_ctx {
   uint8_t* pre_status = nullptr;   // [n]
   PreemptOut* pre_out = nullptr;
   int32_t* pre_victims = nullptr;  // [kPreemptMaxPods]
+  // nominated pods (ks_load_nominated, ks_nominated.h): the caller's rows on the host -- the device table is rebuilt
+  // whole from them on every change (tens to hundreds of rows) -- and the rows at ks_checkpoint
+  struct NomRow {
+    int32_t node, prio;
+    int64_t id;
+    int64_t req[kNomWords];
+  };
+  std::vector<NomRow> h_nom, h_nom_ckpt;
+  void* nom_blob = nullptr;        // the CSR table, then the overlay's output
+  DevNominated nomt{};             // beg == nullptr: no table
+  uint32_t* nom_fit = nullptr;     // [n] nominated_overlay_kernel's Fit reason bits
   // PodTopologySpread / InterPodAffinity (ks_topo.h): node columns in the node blob (counters mutable, zone
   // read-only), the normalizing-weight table, the topology step's scratch and one-candidate set
   int32_t topo_nkeys = 0, topo_ndom = 1, topo_nprops = 0;
@@ -1176,6 +1189,15 @@ struct ks_ctx {
   do {                                                                                       \
     hipError_t e_ = (expr);                                                                  \
     if (e_ != hipSuccess) KS_FAIL(ctx, KS_EHIP, "%s failed: %s", #expr, hipGetErrorString(e_)); \
+  } while (0)
+
+// The entry points whose pods carry no priority refuse a loaded table instead of ignoring it
+#define KS_NOM_REFUSE(ctx, who)                                                                                      \
+  do {                                                                                                               \
+    if (!(ctx)->h_nom.empty())                                                                                       \
+      KS_FAIL(ctx, KS_EUNSUPPORTED, "%s: a nominated table is loaded (%zu pods) and this entry point carries no pod " \
+                                    "priority; use the *_nominated entry points or clear it (ks_load_nominated m = 0)", \
+              who, (ctx)->h_nom.size());                                                                             \
   } while (0)
 
 static int dev_alloc(ks_ctx* ctx, void** p, size_t bytes) {
@@ -1508,6 +1530,7 @@ void ks_destroy(ks_ctx* ctx) {
   p = ctx->pipe; dev_free(p);
   p = ctx->pipe_top; dev_free(p);
   dev_free(ctx->npod_blob);
+  dev_free(ctx->nom_blob);
   dev_free(ctx->topo_blob);
   for (PodStage* ps : {&ctx->st, &ctx->est, &ctx->ast}) {
     void* t = ps->topo;
@@ -1891,6 +1914,12 @@ int ks_load_nodes(ks_ctx* ctx, const ks_node_cols* nodes, int64_t n) {
   // the node-pod table (ks_load_node_pods) is indexed by the old node rows and its per-call scratch is sized to the
   // old node count: drop it, so ks_preempt returns KS_ESTATE until it is reloaded for these nodes
   dev_free(ctx->npod_blob);
+  // ... and the nominated table with its checkpoint: its rows name the old node rows (reload it for these nodes)
+  dev_free(ctx->nom_blob);
+  ctx->nomt = DevNominated{};
+  ctx->nom_fit = nullptr;
+  ctx->h_nom.clear();
+  ctx->h_nom_ckpt.clear();
   ctx->npt = DevNodePods{};
   ctx->pre_cand = nullptr;
   ctx->pre_vrank = nullptr;
@@ -3551,6 +3580,7 @@ static void bind_mode(ks_ctx* ctx, bool required) {
 int ks_stage_pods(ks_ctx* ctx, const ks_pod_cols* pods, int32_t p) {
   if (!ctx || !pods || p < 0) return ctx ? (ctx->err = "ks_stage_pods: bad args", KS_EINVAL) : KS_EINVAL;
   if (!ctx->node_blob) KS_FAIL(ctx, KS_ESTATE, "ks_stage_pods before ks_load_nodes");
+  KS_NOM_REFUSE(ctx, "ks_stage_pods / ks_schedule");
   if (ctx->cfg.quota.enable && pods->quota && !ctx->quota_blob)
     KS_FAIL(ctx, KS_ESTATE, "ElasticQuota enabled but ks_load_quotas not called");
   if (int rc = validate_pods(ctx, pods, p); rc != KS_OK) return rc;
@@ -4303,6 +4333,7 @@ static int launch_pass(ks_ctx* ctx, int32_t ppw, int sweep_blocks, const PipeSha
 
 static int schedule_staged_impl(ks_ctx* ctx) {
   if (!ctx->node_blob) KS_FAIL(ctx, KS_ESTATE, "schedule before ks_load_nodes");
+  KS_NOM_REFUSE(ctx, "ks_schedule_staged");
   if (ctx->staged_stale)
     KS_FAIL(ctx, KS_ESTATE, "ks_schedule_staged: the staged batch predates a table reload; call ks_stage_pods again");
   HIPCHK(ctx, hipSetDevice(ctx->device));
@@ -4523,6 +4554,128 @@ int ks_schedule(ks_ctx* ctx, const ks_pod_cols* pods, int32_t p, ks_result* out)
   return ks_fetch_results(ctx, out, p);
 }
 
+// ---- nominated pods (ks_nominated.h) ----
+
+// The device table from ctx->h_nom: CSR by node, a node's entries in descending priority (equal priorities in caller
+// order), the list of nodes with entries, and the overlay kernel's [n] output behind them.  No rows: no table.
+static int nom_install(ks_ctx* ctx) {
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));  // (a kernel of the last call may still read the old table)
+  dev_free(ctx->nom_blob);
+  ctx->nomt = DevNominated{};
+  ctx->nom_fit = nullptr;
+  const size_t m = ctx->h_nom.size(), n = (size_t)ctx->n;
+  if (m == 0) return KS_OK;
+  std::vector<int32_t> order(m);
+  for (size_t i = 0; i < m; ++i) order[i] = (int32_t)i;
+  const auto& rows = ctx->h_nom;
+  std::stable_sort(order.begin(), order.end(), [&](int32_t x, int32_t y) {
+    if (rows[x].node != rows[y].node) return rows[x].node < rows[y].node;
+    return rows[x].prio > rows[y].prio;
+  });
+  std::vector<int64_t> beg(n + 1, 0);
+  std::vector<int32_t> nodes;
+  for (size_t i = 0; i < m; ++i) ++beg[(size_t)rows[i].node + 1];
+  for (size_t i = 0; i < n; ++i) {
+    if (beg[i + 1]) nodes.push_back((int32_t)i);
+    beg[i + 1] += beg[i];
+  }
+  size_t off = 0;
+  auto take = [&](size_t bytes) { const size_t o = off; off = align16(off + bytes); return o; };
+  const size_t o_beg = take((n + 1) * 8), o_prio = take(m * 4), o_id = take(m * 8), o_req = take(m * 8 * kNomWords),
+               o_nodes = take(nodes.size() * 4), up = off, o_fit = take(std::max<size_t>(n, 1) * 4);
+  std::vector<unsigned char> h(up, 0);
+  memcpy(h.data() + o_beg, beg.data(), (n + 1) * 8);
+  memcpy(h.data() + o_nodes, nodes.data(), nodes.size() * 4);
+  for (size_t pos = 0; pos < m; ++pos) {
+    const ks_ctx::NomRow& r = rows[(size_t)order[pos]];
+    memcpy(h.data() + o_prio + pos * 4, &r.prio, 4);
+    memcpy(h.data() + o_id + pos * 8, &r.id, 8);
+    for (int d = 0; d < kNomWords; ++d) memcpy(h.data() + o_req + ((size_t)d * m + pos) * 8, &r.req[d], 8);
+  }
+  if (dev_alloc(ctx, &ctx->nom_blob, off) != KS_OK) return KS_ENOMEM;
+  HIPCHK(ctx, hipMemcpyAsync(ctx->nom_blob, h.data(), up, hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+  unsigned char* b = (unsigned char*)ctx->nom_blob;
+  DevNominated& t = ctx->nomt;
+  t.beg = (const int64_t*)(b + o_beg);
+  t.prio = (const int32_t*)(b + o_prio);
+  t.id = (const int64_t*)(b + o_id);
+  t.req = (const int64_t*)(b + o_req);
+  t.nodes = (const int32_t*)(b + o_nodes);
+  t.m = (int64_t)m;
+  t.nn = (int32_t)nodes.size();
+  ctx->nom_fit = (uint32_t*)(b + o_fit);
+  return KS_OK;
+}
+
+int ks_load_nominated(ks_ctx* ctx, const ks_nominated_cols* cols, int64_t m, size_t sizeof_cols) {
+  if (!ctx || m < 0 || (m > 0 && !cols)) return ctx ? (ctx->err = "ks_load_nominated: bad args", KS_EINVAL) : KS_EINVAL;
+  if (sizeof_cols != sizeof(ks_nominated_cols))
+    KS_FAIL(ctx, KS_EINVAL, "ks_load_nominated: sizeof_cols %zu, this library's ks_nominated_cols has %zu bytes", sizeof_cols,
+            sizeof(ks_nominated_cols));
+  if (!ctx->node_blob) KS_FAIL(ctx, KS_ESTATE, "ks_load_nominated before ks_load_nodes");
+  if (m >= ((int64_t)1 << 31)) KS_FAIL(ctx, KS_EINVAL, "ks_load_nominated: too many pods");
+  if (m > 0) {
+    // the plugins whose Filters read the node's other pods beyond NodeInfo.Requested: adding a nominated pod would
+    // have to add its ports, topology properties, cpuset, devices or reservation, which the table does not carry
+    std::string plug;
+    auto name = [&](bool on, const char* s) {
+      if (on) plug += (plug.empty() ? "" : ", ") + std::string(s);
+    };
+    name((ctx->kc.ports & 1) != 0, "NodePorts");
+    name(ctx->cfg.topology.enable != 0, "PodTopologySpread / InterPodAffinity");
+    name(ctx->kc.numa != 0, "NodeNUMAResource");
+    name(ctx->kc.dev != 0, "DeviceShare");
+    name(ctx->kc.rsv != 0, "Reservation");
+    if (!plug.empty())
+      KS_FAIL(ctx, KS_EUNSUPPORTED, "ks_load_nominated: nominated pods are not modelled with %s (these Filters read "
+                                    "more of the node's pods than their requests)", plug.c_str());
+    if (!cols->node || !cols->priority || !cols->id)
+      KS_FAIL(ctx, KS_EINVAL, "ks_load_nominated: node, priority and id are required");
+  }
+  std::vector<ks_ctx::NomRow> rows((size_t)m);
+  if (m > 0) {
+    const int64_t* reqc[kNomWords] = {cols->req_milli_cpu, cols->req_memory, cols->req_ephemeral, cols->req_scalar[0],
+                                      cols->req_scalar[1], cols->req_scalar[2], cols->req_scalar[3]};
+    for (int d = 0; d < kNomWords; ++d)
+      if (int rc = check_range64(ctx, reqc[d], m, "nominated pod request"); rc != KS_OK) return rc;
+    std::vector<int64_t> ids(cols->id, cols->id + m);
+    std::sort(ids.begin(), ids.end());
+    for (int64_t i = 0; i < m; ++i) {
+      if (ids[(size_t)i] < 0) KS_FAIL(ctx, KS_EINVAL, "ks_load_nominated: id %lld is negative", (long long)ids[(size_t)i]);
+      if (i && ids[(size_t)i] == ids[(size_t)i - 1])
+        KS_FAIL(ctx, KS_EINVAL, "ks_load_nominated: id %lld listed twice", (long long)ids[(size_t)i]);
+    }
+    for (int64_t i = 0; i < m; ++i) {
+      const int32_t nd = cols->node[i];
+      if (nd < 0 || nd >= ctx->n)
+        KS_FAIL(ctx, KS_EINVAL, "ks_load_nominated: pod %lld nominated to node %d outside [0, %lld)", (long long)i, nd,
+                (long long)ctx->n);
+      ks_ctx::NomRow& r = rows[(size_t)i];
+      r.node = nd;
+      r.prio = cols->priority[i];
+      r.id = cols->id[i];
+      for (int d = 0; d < kNomWords; ++d) r.req[d] = reqc[d] ? reqc[d][i] : 0;
+    }
+  }
+  ctx->h_nom.swap(rows);
+  return nom_install(ctx);
+}
+
+int ks_delete_nominated(ks_ctx* ctx, const int64_t* ids, int64_t m) {
+  if (!ctx || m < 0 || (m > 0 && !ids)) return ctx ? (ctx->err = "ks_delete_nominated: bad args", KS_EINVAL) : KS_EINVAL;
+  if (!ctx->node_blob) KS_FAIL(ctx, KS_ESTATE, "ks_delete_nominated before ks_load_nodes");
+  std::vector<int64_t> gone(ids, ids + m);
+  std::sort(gone.begin(), gone.end());
+  const size_t before = ctx->h_nom.size();
+  ctx->h_nom.erase(std::remove_if(ctx->h_nom.begin(), ctx->h_nom.end(),
+                                  [&](const ks_ctx::NomRow& r) { return std::binary_search(gone.begin(), gone.end(), r.id); }),
+                   ctx->h_nom.end());
+  if (ctx->h_nom.size() == before) return KS_OK;
+  return nom_install(ctx);
+}
+
 int ks_checkpoint(ks_ctx* ctx) {
   if (!ctx || !ctx->node_blob) return ctx ? (ctx->err = "ks_checkpoint before ks_load_nodes", KS_ESTATE) : KS_EINVAL;
   if (!ctx->ckpt_blob && dev_alloc(ctx, &ctx->ckpt_blob, ctx->mut_bytes) != KS_OK) return KS_ENOMEM;
@@ -4545,6 +4698,7 @@ int ks_checkpoint(ks_ctx* ctx) {
   }
   HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
   ctx->h_dev_assumed_ckpt = ctx->h_dev_assumed;
+  ctx->h_nom_ckpt = ctx->h_nom;
   return KS_OK;
 }
 
@@ -4569,6 +4723,10 @@ int ks_restore(ks_ctx* ctx) {
   }
   ctx->h_dev_assumed = ctx->h_dev_assumed_ckpt;
   HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+  if (!ctx->h_nom.empty() || !ctx->h_nom_ckpt.empty()) {  // the nominated table as it was at the checkpoint
+    ctx->h_nom = ctx->h_nom_ckpt;
+    if (int rc = nom_install(ctx); rc != KS_OK) return rc;
+  }
   return KS_OK;
 }
 
@@ -4770,8 +4928,15 @@ int ks_update_reservation_usage(ks_ctx* ctx, const int32_t* rows, const int64_t*
 // One pod's evaluation on ctx->stream into the context's evaluation buffer (ks_eval_pod and ks_eval_pod_summary):
 // validation, staging, the evaluation kernel and every normalization; eb's dr / ds / dt hold the result once the
 // stream reaches this point.  Nothing is copied back and the stream is not synchronized.
-static int eval_pod_launch(ks_ctx* ctx, const ks_pod_cols* pod, const char* who, EvBuf& eb) {
+// nom != NULL (the *_nominated entry points): the nominated table applies for that pod -- the overlay kernel's Fit bits
+// are OR-ed into the reasons inside the evaluation kernel; only >= 0: the normalizations run over that node alone when
+// it is feasible.  Without nom a loaded table refuses the call.
+static int eval_pod_launch(ks_ctx* ctx, const ks_pod_cols* pod, const char* who, EvBuf& eb,
+                           const ks_nomination* nom = nullptr, int32_t only = -1) {
   if (!ctx->node_blob) KS_FAIL(ctx, KS_ESTATE, "%s before ks_load_nodes", who);
+  if (!nom) KS_NOM_REFUSE(ctx, who);
+  if (nom && (nom->nominated_node < -1 || nom->nominated_node >= ctx->n))
+    KS_FAIL(ctx, KS_EINVAL, "%s: nominated node %d out of range", who, nom->nominated_node);
   if (int rc = validate_pods(ctx, pod, 1); rc != KS_OK) return rc;
   bind_mode(ctx, ctx->val_bind_required);
   HIPCHK(ctx, hipSetDevice(ctx->device));
@@ -4785,6 +4950,23 @@ static int eval_pod_launch(ks_ctx* ctx, const ks_pod_cols* pod, const char* who,
   int32_t *draw = eb.draw, *dhi = eb.dhi, *ddraw = eb.ddraw, *dtraw = eb.dtraw, *daraw = eb.daraw;
   const int threads = 256;
   const int blocks = (int)((n + threads - 1) / threads);
+  const uint32_t* nom_fit = nullptr;
+  if (nom && ctx->nomt.beg && blocks > 0) {
+    // Fit with the nominated pods added, on the nodes that have any (a profile with topology terms has no table)
+    const NomWho nw{nom->self_id, nom->priority};
+    const dim3 grid((unsigned)((ctx->nomt.nn + 3) / 4));
+    HIPCHK(ctx, hipMemsetAsync(ctx->nom_fit, 0, (size_t)n * 4, ctx->stream));
+    if (ctx->nsc == 0)
+      hipLaunchKernelGGL(nominated_overlay_kernel<0>, grid, dim3(256), 0, ctx->stream, ctx->nomt, ctx->d, ctx->kc,
+                         (const PodRec*)ctx->est.recs, nw, ctx->nom_fit);
+    else if (ctx->nsc == 2)
+      hipLaunchKernelGGL(nominated_overlay_kernel<2>, grid, dim3(256), 0, ctx->stream, ctx->nomt, ctx->d, ctx->kc,
+                         (const PodRec*)ctx->est.recs, nw, ctx->nom_fit);
+    else
+      hipLaunchKernelGGL(nominated_overlay_kernel<4>, grid, dim3(256), 0, ctx->stream, ctx->nomt, ctx->d, ctx->kc,
+                         (const PodRec*)ctx->est.recs, nw, ctx->nom_fit);
+    nom_fit = ctx->nom_fit;
+  }
   if (blocks > 0 && ctx->cfg.topology.enable && ctx->est.topo) {
     // PodTopologySpread / InterPodAffinity: their PreFilter sums, every Filter (theirs folded into the evaluation
     // kernel), then every normalization over the nodes all Filters leave (the topology step's kernels)
@@ -4798,16 +4980,16 @@ static int eval_pod_launch(ks_ctx* ctx, const ks_pod_cols* pod, const char* who,
   } else if (blocks > 0) {
     HIPCHK(ctx, launch_eval_debug(ctx->nsc, blocks, ctx->stream, ctx->d, ctx->drv, ctx->ddv, ctx->dnv, ctx->kc,
                                   ctx->est.recs, n, dr, ds, dt, draw, dhi, ddraw, ctx->est.stat, dtraw, daraw, nullptr,
-                                  kernel_feat(ctx), ctx->numa_w));
+                                  kernel_feat(ctx), ctx->numa_w, nom_fit));
     if (ctx->kc.dev)
       hipLaunchKernelGGL(dev_normalize_debug_kernel, dim3(1), dim3(1024), 0, ctx->stream, n, dr, ddraw, ds, dt,
                          ctx->cfg.deviceshare.plugin_weight);
     if (ctx->kc.taint & 2)
       hipLaunchKernelGGL(stat_normalize_debug_kernel, dim3(1), dim3(1024), 0, ctx->stream, n, dr, dtraw, ds, dt,
-                         ctx->cfg.taint.plugin_weight, KS_SCORE_TAINT, 1);
+                         ctx->cfg.taint.plugin_weight, KS_SCORE_TAINT, 1, only);
     if (ctx->kc.aff & 2)
       hipLaunchKernelGGL(stat_normalize_debug_kernel, dim3(1), dim3(1024), 0, ctx->stream, n, dr, daraw, ds, dt,
-                         ctx->cfg.affinity.plugin_weight, KS_SCORE_NODE_AFFINITY, 0);
+                         ctx->cfg.affinity.plugin_weight, KS_SCORE_NODE_AFFINITY, 0, only);
     if (ctx->kc.rsv)
       hipLaunchKernelGGL(rsv_normalize_debug_kernel, dim3(1), dim3(1024), 0, ctx->stream, n, dr, draw, dhi, ds, dt,
                          ctx->cfg.reservation.plugin_weight);
@@ -4816,10 +4998,10 @@ static int eval_pod_launch(ks_ctx* ctx, const ks_pod_cols* pod, const char* who,
   return KS_OK;
 }
 
-int ks_eval_pod(ks_ctx* ctx, const ks_pod_cols* pod, uint32_t* reasons, int64_t* scores, int64_t* total) {
-  if (!ctx || !pod) return ctx ? (ctx->err = "ks_eval_pod: bad args", KS_EINVAL) : KS_EINVAL;
+static int eval_pod_impl(ks_ctx* ctx, const ks_pod_cols* pod, const ks_nomination* nom, const char* who,
+                         uint32_t* reasons, int64_t* scores, int64_t* total) {
   EvBuf eb;
-  if (int rc = eval_pod_launch(ctx, pod, "ks_eval_pod", eb); rc != KS_OK) return rc;
+  if (int rc = eval_pod_launch(ctx, pod, who, eb, nom); rc != KS_OK) return rc;
   const int64_t n = ctx->n;
   const uint32_t* dr = eb.dr;
   const int64_t *ds = eb.ds, *dt = eb.dt;
@@ -4828,6 +5010,17 @@ int ks_eval_pod(ks_ctx* ctx, const ks_pod_cols* pod, uint32_t* reasons, int64_t*
   if (total && n) HIPCHK(ctx, hipMemcpyAsync(total, dt, (size_t)n * 8, hipMemcpyDeviceToHost, ctx->stream));
   HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
   return KS_OK;
+}
+
+int ks_eval_pod(ks_ctx* ctx, const ks_pod_cols* pod, uint32_t* reasons, int64_t* scores, int64_t* total) {
+  if (!ctx || !pod) return ctx ? (ctx->err = "ks_eval_pod: bad args", KS_EINVAL) : KS_EINVAL;
+  return eval_pod_impl(ctx, pod, nullptr, "ks_eval_pod", reasons, scores, total);
+}
+
+int ks_eval_pod_nominated(ks_ctx* ctx, const ks_pod_cols* pod, const ks_nomination* who, uint32_t* reasons,
+                          int64_t* scores, int64_t* total) {
+  if (!ctx || !pod || !who) return ctx ? (ctx->err = "ks_eval_pod_nominated: bad args", KS_EINVAL) : KS_EINVAL;
+  return eval_pod_impl(ctx, pod, who, "ks_eval_pod_nominated", reasons, scores, total);
 }
 
 int ks_eval_pod_debug(ks_ctx* ctx, const ks_pod_cols* pod, uint32_t* reasons, int64_t* scores, int64_t* total) {
@@ -4875,17 +5068,19 @@ static int sum_buffers(ks_ctx* ctx, SumBuf& b) {
   return KS_OK;
 }
 
-int ks_eval_pod_summary(ks_ctx* ctx, const ks_pod_cols* pod, uint32_t unresolvable_mask, int32_t top_n,
-                        ks_pod_summary* out, int32_t* top_nodes, int64_t* top_totals, int64_t* top_scores,
-                        uint64_t* feasible_bits, uint64_t* unresolvable_bits) {
-  if (!ctx || !pod) return ctx ? (ctx->err = "ks_eval_pod_summary: bad args", KS_EINVAL) : KS_EINVAL;
-  if (!out) KS_FAIL(ctx, KS_EINVAL, "ks_eval_pod_summary: out is NULL");
+static int eval_pod_summary_impl(ks_ctx* ctx, const ks_pod_cols* pod, const ks_nomination* nom, const char* who,
+                                 uint32_t unresolvable_mask, int32_t top_n, ks_pod_summary* out, int32_t* top_nodes,
+                                 int64_t* top_totals, int64_t* top_scores, uint64_t* feasible_bits,
+                                 uint64_t* unresolvable_bits) {
+  if (!out) KS_FAIL(ctx, KS_EINVAL, "%s: out is NULL", who);
   if (top_n < 0 || top_n > KS_SUMMARY_MAX_TOP)
-    KS_FAIL(ctx, KS_EINVAL, "ks_eval_pod_summary: top_n %d outside [0, %d]", top_n, KS_SUMMARY_MAX_TOP);
+    KS_FAIL(ctx, KS_EINVAL, "%s: top_n %d outside [0, %d]", who, top_n, KS_SUMMARY_MAX_TOP);
   if (top_n > 0 && !top_nodes && !top_totals && !top_scores)
-    KS_FAIL(ctx, KS_EINVAL, "ks_eval_pod_summary: top_n %d without a top_nodes, top_totals or top_scores buffer", top_n);
+    KS_FAIL(ctx, KS_EINVAL, "%s: top_n %d without a top_nodes, top_totals or top_scores buffer", who, top_n);
   EvBuf eb;
-  if (int rc = eval_pod_launch(ctx, pod, "ks_eval_pod_summary", eb); rc != KS_OK) return rc;
+  // the pod's own nominated node, tried first: when it is feasible it is the whole feasible set
+  const int32_t only = nom ? nom->nominated_node : -1;
+  if (int rc = eval_pod_launch(ctx, pod, who, eb, nom, only); rc != KS_OK) return rc;
   const int64_t n = ctx->n;
   memset(out, 0, sizeof(*out));
   out->best_node = -1;
@@ -4898,7 +5093,7 @@ int ks_eval_pod_summary(ks_ctx* ctx, const ks_pod_cols* pod, uint32_t unresolvab
   if (int rc = sum_buffers(ctx, sb); rc != KS_OK) return rc;
   const int32_t k = top_n > 1 ? top_n : 1;  // the winner is row 0 whatever top_n is
   hipLaunchKernelGGL(summary_block_kernel, dim3((unsigned)sb.blocks), dim3(kSumThreads), 0, ctx->stream, n, eb.dr, eb.dt,
-                     unresolvable_mask, k, sb.fbits, sb.ubits, sb.blk_bins, sb.part_tot, sb.part_idx);
+                     unresolvable_mask, k, sb.fbits, sb.ubits, sb.blk_bins, sb.part_tot, sb.part_idx, only);
   hipLaunchKernelGGL(summary_merge_kernel, dim3(1), dim3(kSumMergeWaves * 64), 0, ctx->stream, n, (int32_t)sb.blocks,
                      top_n, k, sb.blk_bins, sb.part_tot, sb.part_idx, eb.ds, sb.out);
   HIPCHK(ctx, hipGetLastError());
@@ -4916,6 +5111,23 @@ int ks_eval_pod_summary(ks_ctx* ctx, const ks_pod_cols* pod, uint32_t unresolvab
   if (feasible_bits) memcpy(feasible_bits, hb, (size_t)sb.nwords * 8);
   if (unresolvable_bits) memcpy(unresolvable_bits, hb + sb.nwords, (size_t)sb.nwords * 8);
   return KS_OK;
+}
+
+int ks_eval_pod_summary(ks_ctx* ctx, const ks_pod_cols* pod, uint32_t unresolvable_mask, int32_t top_n,
+                        ks_pod_summary* out, int32_t* top_nodes, int64_t* top_totals, int64_t* top_scores,
+                        uint64_t* feasible_bits, uint64_t* unresolvable_bits) {
+  if (!ctx || !pod) return ctx ? (ctx->err = "ks_eval_pod_summary: bad args", KS_EINVAL) : KS_EINVAL;
+  return eval_pod_summary_impl(ctx, pod, nullptr, "ks_eval_pod_summary", unresolvable_mask, top_n, out, top_nodes,
+                               top_totals, top_scores, feasible_bits, unresolvable_bits);
+}
+
+int ks_eval_pod_summary_nominated(ks_ctx* ctx, const ks_pod_cols* pod, const ks_nomination* who,
+                                  uint32_t unresolvable_mask, int32_t top_n, ks_pod_summary* out, int32_t* top_nodes,
+                                  int64_t* top_totals, int64_t* top_scores, uint64_t* feasible_bits,
+                                  uint64_t* unresolvable_bits) {
+  if (!ctx || !pod || !who) return ctx ? (ctx->err = "ks_eval_pod_summary_nominated: bad args", KS_EINVAL) : KS_EINVAL;
+  return eval_pod_summary_impl(ctx, pod, who, "ks_eval_pod_summary_nominated", unresolvable_mask, top_n, out, top_nodes,
+                               top_totals, top_scores, feasible_bits, unresolvable_bits);
 }
 
 // Unreserve of every plugin + the scheduler cache's ForgetPod for one pod (ks_unreserve; one thread, a few dozen
@@ -5377,6 +5589,13 @@ int ks_load_node_pods(ks_ctx* ctx, const ks_node_pod_cols* pc, int64_t m, const 
 int ks_preempt(ks_ctx* ctx, const ks_pod_cols* pod, int32_t priority, uint32_t flags, int32_t nominated,
                const uint8_t* unresolvable, ks_preempt_result* out, int32_t* victims, int32_t victims_cap,
                uint8_t* node_status) {
+  return ks_preempt_nominated(ctx, pod, priority, flags, nominated, -1, unresolvable, out, victims, victims_cap,
+                              node_status);
+}
+
+int ks_preempt_nominated(ks_ctx* ctx, const ks_pod_cols* pod, int32_t priority, uint32_t flags, int32_t nominated,
+                         int64_t self_id, const uint8_t* unresolvable, ks_preempt_result* out, int32_t* victims,
+                         int32_t victims_cap, uint8_t* node_status) {
   if (!ctx || !pod || !out || victims_cap < 0 || (victims_cap > 0 && !victims))
     return ctx ? (ctx->err = "ks_preempt: bad args", KS_EINVAL) : KS_EINVAL;
   if (!ctx->npod_blob) KS_FAIL(ctx, KS_ESTATE, "ks_preempt before ks_load_node_pods");
@@ -5421,6 +5640,8 @@ int ks_preempt(ks_ctx* ctx, const ks_pod_cols* pod, int32_t priority, uint32_t f
   a.prio = priority;
   a.pflags = flags;
   a.nominated = nominated;
+  a.nom = ctx->nomt;  // (beg == nullptr: no table, the dry runs as without one)
+  a.self_id = self_id;
   a.unresolvable = dunres;
   a.n = n;
   a.cand = ctx->pre_cand;

@@ -13,7 +13,7 @@ template <int NSC, int FEAT, int NW = kNumaDev>
 __global__ __launch_bounds__(256) void eval_debug_kernel(DevNodes d, const DevRsv* rv, const DevDev* dv, const DevNuma* nv, Cfg c, const PodRec* pod, int64_t n,
                                   uint32_t* reasons, int64_t* scores, int64_t* total, int32_t* raw, int32_t* hiord,
                                   int32_t* draw, const PodStat* pstat, int32_t* traw, int32_t* araw,
-                                  TopoKArgs tk, int32_t topo) {
+                                  TopoKArgs tk, int32_t topo, const uint32_t* nom_fit) {
   __shared__ TopoLds tl;
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   const bool valid = i < n;
@@ -42,6 +42,9 @@ __global__ __launch_bounds__(256) void eval_debug_kernel(DevNodes d, const DevRs
         c, p, r, [&](auto&& f) { return f(RsvG<false>(*rv, i)); },
         [&]() { return DevGView{*dv, i}; }, [&]() { return NumaGViewT<NW>{*nv, i}; }, &ro);
     if (c.stat) stat_eval(c, *ps, th, ts, lb, hp, o);
+    // RunFilterPluginsWithNominatedPods: Fit's verdict with the node's nominated pods added (ks_nominated.h), before
+    // feasibility, the scores and the normalizations' inputs are formed
+    if (nom_fit) o.reasons |= nom_fit[i];
     reasons[i] = o.reasons;
     // Fit + LoadAware + NUMA + BalancedAllocation part (the normalized plugins are added by the normalize kernels)
     total[i] = o.reasons ? -1
@@ -78,28 +81,28 @@ template <int NSC>
 static void launch_nsc(int feat, int blocks, hipStream_t s, DevNodes d, const DevRsv* rv, const DevDev* dv,
                        const DevNuma* nv, Cfg c, const PodRec* pod, int64_t n, uint32_t* reasons, int64_t* scores,
                        int64_t* total, int32_t* raw, int32_t* hiord, int32_t* draw, const PodStat* pstat, int32_t* traw,
-                       int32_t* araw, const TopoKArgs& t, int32_t on, int numa_w) {
+                       int32_t* araw, const TopoKArgs& t, int32_t on, int numa_w, const uint32_t* nom_fit) {
   if (feat != 0 && feat != 4 && numa_w == kNumaWide)  // a context at NUMA width 8 (ks_numa_wide.h)
-    hipLaunchKernelGGL((eval_debug_kernel<NSC, 31, kNumaWide>), dim3(blocks), dim3(256), 0, s, d, rv, dv, nv, c, pod, n, reasons, scores, total, raw, hiord, draw, pstat, traw, araw, t, on);
+    hipLaunchKernelGGL((eval_debug_kernel<NSC, 31, kNumaWide>), dim3(blocks), dim3(256), 0, s, d, rv, dv, nv, c, pod, n, reasons, scores, total, raw, hiord, draw, pstat, traw, araw, t, on, nom_fit);
   else if (feat == 0)
-    hipLaunchKernelGGL((eval_debug_kernel<NSC, 0>), dim3(blocks), dim3(256), 0, s, d, rv, dv, nv, c, pod, n, reasons, scores, total, raw, hiord, draw, pstat, traw, araw, t, on);
+    hipLaunchKernelGGL((eval_debug_kernel<NSC, 0>), dim3(blocks), dim3(256), 0, s, d, rv, dv, nv, c, pod, n, reasons, scores, total, raw, hiord, draw, pstat, traw, araw, t, on, nom_fit);
   else if (feat == 4)
-    hipLaunchKernelGGL((eval_debug_kernel<NSC, 4>), dim3(blocks), dim3(256), 0, s, d, rv, dv, nv, c, pod, n, reasons, scores, total, raw, hiord, draw, pstat, traw, araw, t, on);
+    hipLaunchKernelGGL((eval_debug_kernel<NSC, 4>), dim3(blocks), dim3(256), 0, s, d, rv, dv, nv, c, pod, n, reasons, scores, total, raw, hiord, draw, pstat, traw, araw, t, on, nom_fit);
   else
-    hipLaunchKernelGGL((eval_debug_kernel<NSC, 31>), dim3(blocks), dim3(256), 0, s, d, rv, dv, nv, c, pod, n, reasons, scores, total, raw, hiord, draw, pstat, traw, araw, t, on);
+    hipLaunchKernelGGL((eval_debug_kernel<NSC, 31>), dim3(blocks), dim3(256), 0, s, d, rv, dv, nv, c, pod, n, reasons, scores, total, raw, hiord, draw, pstat, traw, araw, t, on, nom_fit);
 }
 
 hipError_t launch_eval_debug(int nsc, int blocks, hipStream_t s, DevNodes d, const DevRsv* rv, const DevDev* dv,
                              const DevNuma* nv, Cfg c, const PodRec* pod, int64_t n, uint32_t* reasons,
                              int64_t* scores, int64_t* total, int32_t* raw, int32_t* hiord, int32_t* draw,
                              const PodStat* pstat, int32_t* traw, int32_t* araw, const TopoKArgs* tk, int feat,
-                             int numa_w) {
+                             int numa_w, const uint32_t* nom_fit) {
   const TopoKArgs t = tk ? *tk : TopoKArgs{};
   const int32_t on = tk ? 1 : 0;
   const int f = (feat == 0 || feat == 4) ? feat : 15;
-  if (nsc == 0) launch_nsc<0>(f, blocks, s, d, rv, dv, nv, c, pod, n, reasons, scores, total, raw, hiord, draw, pstat, traw, araw, t, on, numa_w);
-  else if (nsc == 2) launch_nsc<2>(f, blocks, s, d, rv, dv, nv, c, pod, n, reasons, scores, total, raw, hiord, draw, pstat, traw, araw, t, on, numa_w);
-  else launch_nsc<4>(f, blocks, s, d, rv, dv, nv, c, pod, n, reasons, scores, total, raw, hiord, draw, pstat, traw, araw, t, on, numa_w);
+  if (nsc == 0) launch_nsc<0>(f, blocks, s, d, rv, dv, nv, c, pod, n, reasons, scores, total, raw, hiord, draw, pstat, traw, araw, t, on, numa_w, nom_fit);
+  else if (nsc == 2) launch_nsc<2>(f, blocks, s, d, rv, dv, nv, c, pod, n, reasons, scores, total, raw, hiord, draw, pstat, traw, araw, t, on, numa_w, nom_fit);
+  else launch_nsc<4>(f, blocks, s, d, rv, dv, nv, c, pod, n, reasons, scores, total, raw, hiord, draw, pstat, traw, araw, t, on, numa_w, nom_fit);
   return hipGetLastError();
 }
 

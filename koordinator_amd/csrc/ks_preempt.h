@@ -13,7 +13,9 @@
 //                           order does not matter); the Filter plugins run once on that; the PDB split
 //                           (filterPodsWithPDBViolation :223-265) ranks, per budget, its members among the potential
 //                           victims with ballots (a pod may match several budgets); the reprieve loop (:172-216) is wave-uniform over the victims in
-//                           order, each step reading the pod's 15 request words from the lane that holds it.
+//                           order, each step reading the pod's 15 request words from the lane that holds it.  With a
+//                           nominated table (ks_nominated.h) the node's nominated sum for the preemptor's priority
+//                           is added once, one wave reduction, before the first Fit check.
 //   preempt_select_kernel   one workgroup: PodEligibleToPreemptOthers (:60-97) on the nominated node, the candidate
 //                           counts, the lexicographic minimum of pickOneNodeForPreemption's keys (fewest PDB violations,
 //                           lowest first-victim priority, lowest priority sum, fewest victims, latest earliest start of
@@ -21,6 +23,7 @@
 #pragma once
 
 #include "ks_device.h"
+#include "ks_nominated.h"
 #include "ks_rsv.h"
 
 namespace ks {
@@ -76,6 +79,8 @@ struct PreemptArgs {
   int32_t prio;
   uint32_t pflags;  // KS_PREEMPT_*
   int32_t nominated;
+  DevNominated nom;  // the nominated table (ks_nominated.h), beg == null: none
+  int64_t self_id;   // the preemptor's own entry of it, -1 = none
   const uint8_t* unresolvable;  // [n] or null
   int64_t n;
   PreemptCand* cand;  // [n]
@@ -177,6 +182,15 @@ __global__ __launch_bounds__(256) void preempt_dry_run_kernel(PreemptArgs a) {
   for (int k = 0; k < kRsvDims; ++k) free[k] = alloc[k] - (reqn[k] - dreq[k]);
   int64_t pods = (int64_t)gld(d.pod_count + n) - nv;
   const int64_t allowed = gld(d.allowed_pods + n);
+  if (a.nom.beg) {
+    // RunFilterPluginsWithNominatedPods: the node's nominated pods of priority >= the preemptor's (its own entry
+    // excluded) are added to the NodeInfo every Filter run of this dry run sees -- the one below and each reprieve's.
+    // Only Fit reads them; the quota state is not touched (ElasticQuota's AddPod writes a clone no Filter reads).
+    const NomSum ns = nominated_sum(a.nom, n, NomWho{a.self_id, a.prio}, lane);
+#pragma unroll
+    for (int k = 0; k < kRsvDims; ++k) free[k] -= ns.req[k];
+    pods += ns.count;
+  }
   int64_t used[KS_QUOTA_DIMS], limit[KS_QUOTA_DIMS], preq[KS_QUOTA_DIMS];
   const uint32_t lmask = gld(a.q.limit_mask + Q), pmask = gld(a.pq.mask);
 #pragma unroll
@@ -186,7 +200,7 @@ __global__ __launch_bounds__(256) void preempt_dry_run_kernel(PreemptArgs a) {
     limit[k] = gld(a.q.limit + (int64_t)Q * KS_QUOTA_DIMS + k);
     preq[k] = gld(a.pq.req[k]);
   }
-  // ---- RunFilterPluginsWithNominatedPods with every potential victim gone (no nominated pods) ----
+  // ---- RunFilterPluginsWithNominatedPods with every potential victim gone ----
   bool static_ok = true;
   if (a.c.la_filter && !(p.flags & KS_POD_DAEMONSET))
     static_ok = !(gld(d.la_bits + n) & ((p.flags & KS_POD_PROD) ? kLaFailProd : kLaFailNonProd));

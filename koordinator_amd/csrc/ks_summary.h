@@ -12,7 +12,7 @@
 //                         node) pair among the workgroup's by counting the pairs that beat it -- every lane reads the
 //                         same LDS word, a broadcast, so no bank conflicts and no barriers inside the loop -- and the
 //                         first k = max(top_n, 1) ranks go to the workgroup's partial list, padded with a sentinel that
-//                         sorts last.
+//                         sorts last.  With `only` >= 0 and that node feasible, it alone counts as feasible.
 //   summary_merge_kernel  one workgroup of 16 waves.  A wave holds a sorted 64-entry list, one entry per lane, and takes
 //                         a partial list in with one bitonic merge: the elementwise better of the list and the
 //                         reversed partial list holds the 64 best of both as a bitonic sequence, which six
@@ -56,13 +56,16 @@ __global__ __launch_bounds__(kSumThreads) void summary_block_kernel(int64_t n, c
                                                                     uint64_t* __restrict__ ubits,
                                                                     uint32_t* __restrict__ blk_bins,
                                                                     int64_t* __restrict__ part_tot,
-                                                                    int32_t* __restrict__ part_idx) {
+                                                                    int32_t* __restrict__ part_idx, int32_t only) {
   __shared__ uint32_t bins[kSumBins];
   __shared__ int64_t stot[kSumThreads];
   const int tid = (int)threadIdx.x, lane = tid & 63;
   const int64_t i = (int64_t)blockIdx.x * kSumThreads + tid;
   const uint32_t r = i < n ? reasons[i] : 0u;  // (reasons is not padded: no read at or past n)
-  const bool feas = i < n && r == 0u;
+  // only >= 0 (ks_eval_pod_summary_nominated): the pod's nominated node is the whole feasible set when it is feasible
+  // (upstream evaluateNominatedNode); the reason bins and the unresolvable set keep every node's own status
+  const bool one = only >= 0 && reasons[only] == 0u;
+  const bool feas = i < n && r == 0u && (!one || i == (int64_t)only);
   const bool unres = (r & mask) != 0u;
   const int64_t t = feas ? total[i] : kSumNoTotal;
   if (tid < kSumBins) bins[tid] = 0u;

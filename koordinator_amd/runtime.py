@@ -14,8 +14,8 @@ from typing import Optional
 import numpy as np
 
 from . import abi
-from .cluster import (CpuState, DeviceTable, NodePodTable, NumaNodes, NodeState, NodeTable, PodTable, QuotaTable,
-                      QuotaTree, ReservationTable)
+from .cluster import (CpuState, DeviceTable, NodePodTable, NominatedTable, NumaNodes, NodeState, NodeTable, PodTable,
+                      QuotaTable, QuotaTree, ReservationTable)
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("KS_LIB_PATH") or os.path.join(HERE, "libkoordgpu.so")
@@ -104,6 +104,16 @@ def lib() -> C.CDLL:
     L.ks_load_node_pods.argtypes = [vp, C.POINTER(abi.KsNodePodCols), C.c_int64, abi.P32, C.c_int32]
     L.ks_preempt.argtypes = [vp, C.POINTER(abi.KsPodCols), C.c_int32, C.c_uint32, C.c_int32, C.POINTER(C.c_uint8),
                              C.POINTER(abi.KsPreemptResult), abi.P32, C.c_int32, C.POINTER(C.c_uint8)]
+    L.ks_load_nominated.argtypes = [vp, C.POINTER(abi.KsNominatedCols), C.c_int64, C.c_size_t]
+    L.ks_delete_nominated.argtypes = [vp, abi.P64, C.c_int64]
+    L.ks_eval_pod_nominated.argtypes = [vp, C.POINTER(abi.KsPodCols), C.POINTER(abi.KsNomination), abi.PU32, abi.P64,
+                                        abi.P64]
+    L.ks_eval_pod_summary_nominated.argtypes = [vp, C.POINTER(abi.KsPodCols), C.POINTER(abi.KsNomination), C.c_uint32,
+                                                C.c_int32, C.POINTER(abi.KsPodSummary), abi.P32, abi.P64, abi.P64,
+                                                abi.PU64, abi.PU64]
+    L.ks_preempt_nominated.argtypes = [vp, C.POINTER(abi.KsPodCols), C.c_int32, C.c_uint32, C.c_int32, C.c_int64,
+                                       C.POINTER(C.c_uint8), C.POINTER(abi.KsPreemptResult), abi.P32, C.c_int32,
+                                       C.POINTER(C.c_uint8)]
     for name in abi.EXPORTED_SYMBOLS:
         if name not in ("ks_destroy", "ks_last_error"):
             getattr(L, name).restype = C.c_int
@@ -377,17 +387,47 @@ class Evaluator:
     def restore(self):
         self._chk(self.L.ks_restore(self.h))
 
-    def eval_pod(self, pod: PodTable):
+    def load_nominated(self, t: Optional[NominatedTable], sizeof_cols: Optional[int] = None):
+        """Replace the nominated-pod table (ks_load_nominated); None or an empty table clears it."""
+        m = 0 if t is None else t.m
+        cols = abi.KsNominatedCols() if t is None else t.ks()
+        size = C.sizeof(abi.KsNominatedCols) if sizeof_cols is None else int(sizeof_cols)
+        self._chk(self.L.ks_load_nominated(self.h, C.byref(cols), m, size))
+
+    def delete_nominated(self, ids):
+        """The nominated pods with these ids were assumed or deleted, or their nomination was cleared."""
+        ids = np.ascontiguousarray(ids, np.int64).reshape(-1)
+        self._chk(self.L.ks_delete_nominated(self.h, ids.ctypes.data_as(abi.P64), ids.size))
+
+    @staticmethod
+    def _who(priority: int, nominated_node: int = -1, self_id: int = -1) -> abi.KsNomination:
+        return abi.KsNomination(priority=int(priority), nominated_node=int(nominated_node), self_id=int(self_id))
+
+    def eval_pod_nominated(self, pod: PodTable, priority: int, nominated_node: int = -1, self_id: int = -1):
+        """eval_pod with the nominated table applied for a pod of `priority` (ks_eval_pod_nominated)"""
+        return self.eval_pod(pod, who=self._who(priority, nominated_node, self_id))
+
+    def eval_pod_summary_nominated(self, pod: PodTable, priority: int, nominated_node: int = -1, self_id: int = -1,
+                                   **kw):
+        """eval_pod_summary with the nominated table applied (ks_eval_pod_summary_nominated): a feasible
+        nominated_node is the whole feasible set"""
+        return self.eval_pod_summary(pod, who=self._who(priority, nominated_node, self_id), **kw)
+
+    def eval_pod(self, pod: PodTable, who: Optional[abi.KsNomination] = None):
         reasons = np.zeros(max(self.n, 1), np.uint32)
         scores = np.zeros(max(self.n, 1) * abi.KS_NUM_SCORE_PLUGINS, np.int64)
         total = np.zeros(max(self.n, 1), np.int64)
         cols = pod.ks()
-        self._chk(self.L.ks_eval_pod(self.h, C.byref(cols), reasons.ctypes.data_as(abi.PU32),
-                                     scores.ctypes.data_as(abi.P64), total.ctypes.data_as(abi.P64)))
+        outs = (reasons.ctypes.data_as(abi.PU32), scores.ctypes.data_as(abi.P64), total.ctypes.data_as(abi.P64))
+        if who is None:
+            self._chk(self.L.ks_eval_pod(self.h, C.byref(cols), *outs))
+        else:
+            self._chk(self.L.ks_eval_pod_nominated(self.h, C.byref(cols), C.byref(who), *outs))
         n = self.n
         return reasons[:n], scores[: n * abi.KS_NUM_SCORE_PLUGINS].reshape(n, abi.KS_NUM_SCORE_PLUGINS), total[:n]
 
-    def eval_pod_summary(self, pod: PodTable, top_n: int = 0, unresolvable_mask: int = 0, want_bits: bool = False):
+    def eval_pod_summary(self, pod: PodTable, top_n: int = 0, unresolvable_mask: int = 0, want_bits: bool = False,
+                         who: Optional[abi.KsNomination] = None):
         """ks_eval_pod reduced on the device (ks_eval_pod_summary): a dict of nodes, feasible, unresolvable,
         reason_nodes (int64[32], [b] = nodes with reason bit b), best_node / best_total (-1 when nothing fits), and the
         first top_count = min(top_n, feasible) nodes by (total descending, node ascending) as top_nodes, top_totals and
@@ -403,11 +443,14 @@ class Evaluator:
         fbits = np.zeros(words, np.uint64) if want_bits else None
         ubits = np.zeros(words, np.uint64) if want_bits else None
         cols = pod.ks()
-        self._chk(self.L.ks_eval_pod_summary(
-            self.h, C.byref(cols), int(unresolvable_mask) & 0xFFFFFFFF, top_n, C.byref(s),
-            nodes.ctypes.data_as(abi.P32), totals.ctypes.data_as(abi.P64), scores.ctypes.data_as(abi.P64),
-            fbits.ctypes.data_as(abi.PU64) if want_bits else None,
-            ubits.ctypes.data_as(abi.PU64) if want_bits else None))
+        tail = (int(unresolvable_mask) & 0xFFFFFFFF, top_n, C.byref(s),
+                nodes.ctypes.data_as(abi.P32), totals.ctypes.data_as(abi.P64), scores.ctypes.data_as(abi.P64),
+                fbits.ctypes.data_as(abi.PU64) if want_bits else None,
+                ubits.ctypes.data_as(abi.PU64) if want_bits else None)
+        if who is None:
+            self._chk(self.L.ks_eval_pod_summary(self.h, C.byref(cols), *tail))
+        else:
+            self._chk(self.L.ks_eval_pod_summary_nominated(self.h, C.byref(cols), C.byref(who), *tail))
         k = int(s.top_count)
         out = {"nodes": int(s.nodes), "feasible": int(s.feasible), "unresolvable": int(s.unresolvable),
                "reason_nodes": np.array(s.reason_nodes[:], np.int64), "best_node": int(s.best_node),
@@ -486,19 +529,23 @@ class Evaluator:
         self.npods = t.m
 
     def preempt(self, pod: PodTable, priority: int, flags: int = 0, nominated_node: int = -1, unresolvable=None,
-                node_status: bool = False) -> dict:
-        """ElasticQuota PostFilter of pod 0 (ks_preempt): {status, node, victims (node-pod table rows, Victims.Pods
-        order), num_pdb_violations, candidates, potential_nodes[, node_status]}"""
+                node_status: bool = False, self_id: Optional[int] = None) -> dict:
+        """ElasticQuota PostFilter of pod 0 (ks_preempt; ks_preempt_nominated when self_id is given: the preemptor's own
+        row of the nominated table does not count against it): {status, node, victims (node-pod table rows,
+        Victims.Pods order), num_pdb_violations, candidates, potential_nodes[, node_status]}"""
         out = abi.KsPreemptResult()
         cap = max(getattr(self, "npods", 0), 1)
         vic = np.zeros(cap, np.int32)
         ns = np.zeros(max(self.n, 1), np.uint8) if node_status else None
         ur = None if unresolvable is None else np.ascontiguousarray(unresolvable, np.uint8)
         cols = pod if isinstance(pod, abi.KsPodCols) else pod.ks()  # (a prebuilt pointer struct: no per-call rebuild)
-        self._chk(self.L.ks_preempt(self.h, C.byref(cols), int(priority), int(flags), int(nominated_node),
-                                    ur.ctypes.data_as(C.POINTER(C.c_uint8)) if ur is not None else None, C.byref(out),
-                                    vic.ctypes.data_as(abi.P32), cap,
-                                    ns.ctypes.data_as(C.POINTER(C.c_uint8)) if ns is not None else None))
+        tail = (ur.ctypes.data_as(C.POINTER(C.c_uint8)) if ur is not None else None, C.byref(out),
+                vic.ctypes.data_as(abi.P32), cap, ns.ctypes.data_as(C.POINTER(C.c_uint8)) if ns is not None else None)
+        if self_id is None:
+            self._chk(self.L.ks_preempt(self.h, C.byref(cols), int(priority), int(flags), int(nominated_node), *tail))
+        else:
+            self._chk(self.L.ks_preempt_nominated(self.h, C.byref(cols), int(priority), int(flags),
+                                                  int(nominated_node), int(self_id), *tail))
         r = {"status": out.status, "node": out.node, "victims": vic[: out.num_victims].copy(),
              "num_pdb_violations": out.num_pdb_violations, "candidates": out.candidates,
              "potential_nodes": out.potential_nodes}
