@@ -942,14 +942,90 @@ struct Col {
   bool mutable_;    // changed by commits (checkpointed)
 };
 
+// Owner of a hipMalloc'd buffer: move-only, freed when it is reset, assigned over or destroyed (dev_alloc fills it).
+template <class T = void>
+class DevPtr {
+  T* p_ = nullptr;
+
+ public:
+  DevPtr() = default;
+  DevPtr(DevPtr&& o) noexcept : p_(o.p_) { o.p_ = nullptr; }
+  DevPtr& operator=(DevPtr&& o) noexcept {
+    if (this != &o) {
+      reset(o.p_);
+      o.p_ = nullptr;
+    }
+    return *this;
+  }
+  ~DevPtr() { reset(); }
+  T* get() const { return p_; }
+  void reset(T* p = nullptr) {
+    if (p_) (void)hipFree(p_);
+    p_ = p;
+  }
+};
+
+// ... and of a pinned host buffer (host_alloc)
+class HostPtr {
+  void* p_ = nullptr;
+
+ public:
+  HostPtr() = default;
+  HostPtr(HostPtr&& o) noexcept : p_(o.p_) { o.p_ = nullptr; }
+  HostPtr& operator=(HostPtr&& o) noexcept {
+    if (this != &o) {
+      reset(o.p_);
+      o.p_ = nullptr;
+    }
+    return *this;
+  }
+  ~HostPtr() { reset(); }
+  void* get() const { return p_; }
+  void reset(void* p = nullptr) {
+    if (p_) (void)hipHostFree(p_);
+    p_ = p;
+  }
+};
+
+// Owners of the context's stream and events.  ks_ctx declares them before every buffer, so they are destroyed after
+// the buffers are freed.
+struct Stream {
+  hipStream_t h = nullptr;
+  Stream() = default;
+  Stream(const Stream&) = delete;
+  ~Stream() {
+    if (h) (void)hipStreamDestroy(h);
+  }
+  operator hipStream_t() const { return h; }
+};
+struct Event {
+  hipEvent_t h = nullptr;
+  Event() = default;
+  Event(Event&& o) noexcept : h(o.h) { o.h = nullptr; }
+  ~Event() {
+    if (h) (void)hipEventDestroy(h);
+  }
+  operator hipEvent_t() const { return h; }
+};
+
+// One checkpointed region of a table's blob: ks_checkpoint copies live -> ckpt, ks_restore ckpt -> live.  The install
+// that carves the blob fills it in from the offsets and sizes it lays the blob out with.  The CPU-state and NUMA-node installs also seed ckpt at load, the device, reservation and quota
+// installs do not: that difference lies outside the documented contract (ks_checkpoint again after a load) and is
+// kept as it is.
+struct Snap {
+  void* live = nullptr;
+  void* ckpt = nullptr;
+  size_t bytes = 0;
+};
+
 }  // namespace
 
 constexpr int kPipeEvents = 4;  // ring of cross-stream events of the pipelined passes
 
 struct PodStage {
-  void* blob = nullptr;
+  DevPtr<> blob;
   int32_t cap = 0;
-  PodRec* recs = nullptr;       // [cap] built by prep_pods_kernel
+  PodRec* recs = nullptr;       // [cap] built by prep_pods_kernel (view into blob, as stat, results, cols and pq)
   PodStat* stat = nullptr;      // [cap] TaintToleration / NodeAffinity inputs (host-built at staging)
   ks_result* results = nullptr; // [cap]
   DevPodCols cols{};            // the caller's columns in HBM
@@ -958,14 +1034,14 @@ struct PodStage {
   std::vector<uint8_t> h_dyn;   // before the next stage_cols)
   // small batches (ks_eval_pod, ks_assume, ks_preempt, short queues): the column region [cols.cpu, end) packed on the
   // host in its device layout and sent with one copy instead of ~35 (each a HIP API round trip)
-  void* h_pack = nullptr;       // pinned, kPackPods pods
+  HostPtr h_pack;               // pinned, kPackPods pods
   size_t pack_bytes = 0;
   size_t col8 = 0, col4 = 0;    // device column strides of this stage
   // PodTopologySpread / InterPodAffinity (ks_topo.h): per pod its TopoRec, and the stage's query-term and property
   // lists the records point into; ndyn = topology pods of the stage
-  TopoRec* topo = nullptr;
-  uint64_t* topo_terms = nullptr;
-  int32_t* topo_props = nullptr;
+  DevPtr<TopoRec> topo;
+  DevPtr<uint64_t> topo_terms;
+  DevPtr<int32_t> topo_props;
   int32_t topo_cap = 0;
   int64_t topo_tcap = 0, topo_pcap = 0;
   int32_t ndyn = 0;
@@ -990,191 +1066,283 @@ struct LoopGroup {
   int32_t refs = 0;
 };
 
-struct ks_ctx {
-  ks_config cfg{};
-  Cfg kc{};
-  int device = 0;
-  hipStream_t stream = nullptr;
-  std::string err;
-  // nodes
+// ---- the tables of a context.  Each holds what goes with one loaded table: its device blob, the host copy of the
+// device view, the checkpointed regions of the blob (Snap) and the host caches indexed by its rows.  Assigning {} drops
+// the table; reset(n) also sizes the per-node caches that helpers index before the next install.  The fixed-size
+// device copies of the views (drv, ddv, dnv) are allocated once and stay in ks_ctx. ----
+
+struct NodeTable {
   int64_t n = 0, npad = 0, nchunks = 0;
   int nsc = 0;
   DevNodes d{};
   std::vector<Col> cols;
-  void* node_blob = nullptr;
-  void* ckpt_blob = nullptr;
+  DevPtr<> blob;
+  DevPtr<> ckpt;             // the mutable columns at ks_checkpoint (allocated by the first one: "a checkpoint exists")
   size_t mut_bytes = 0;
-  // quotas
+  uint64_t soft_union = 0;   // TaintToleration: OR of every node's PreferNoSchedule taint bits (kPodNormDyn at staging)
+  std::vector<uint8_t> h_pol;     // per node: a NUMA topology policy (numa_flags)
+  int64_t numa_policy_nodes = 0;  // nodes with a NUMA topology policy
+  bool cpu_bind_labels = false;   // a node CPU bind policy was loaded
+  DevPtr<> rdscratch;        // ks_read_nodes: the NodeInfo view of the reservation-restored columns (on demand)
+  DevPtr<uint2> sweep_out;   // pass scratch sized by the padded node count
+};
+
+struct QuotaTable {
   DevQuotas q{};
-  void* quota_blob = nullptr;
-  int64_t* quota_used_ckpt = nullptr;
-  int64_t* quota_npused_ckpt = nullptr;
-  // pods
+  DevPtr<> blob;
+  Snap snap[2];  // used, npused
+};
+
+// host mirror of the caller's reservation rows, for ks_add_reservations / ks_delete_reservations (allocated /
+// assigned are refreshed from the device before each change)
+struct RsvMirror {
+  std::vector<int32_t> node, assigned;
+  std::vector<uint64_t> cls;
+  std::vector<uint32_t> flags, policy, key_mask;
+  std::vector<int64_t> order, rnz_cpu, rnz_mem;
+  std::vector<int64_t> alloc[kRsvDims], allocd[kRsvDims];
+  std::vector<int64_t> dal, dald;  // [row * KS_DEV_WORDS + w]
+  std::vector<uint8_t> live;
+};
+
+// reservations (ks_rsv.h)
+struct RsvTable {
+  DevPtr<> blob;
+  DevRsv rv{};               // host copy of the device table (allocd, assigned, dald: views into blob)
+  bool based = false;        // node columns hold the base restore of rv
+  int32_t ndist = 0;         // distinct order labels
+  int32_t nrows = 0;         // caller rows (deleted ones included)
+  int32_t live = 0;          // rows of the device table (the caller rows not deleted)
+  std::vector<int32_t> perm;    // CSR position -> caller row
+  std::vector<int32_t> h_gi;    // caller reservation row -> CSR position
+  std::vector<int32_t> h_node;  // CSR position -> node
+  RsvMirror rmir;
+  std::vector<uint8_t> h_dev_held;  // per node: a reservation on it holds devices (kDevRsvHeld)
+  bool dev_held_any = false;        // ... on some node (the pass kernels' FEAT bit 16)
+  Snap snap[3];                     // allocd, the devices' allocated, assigned
+  void reset(int64_t n) {
+    *this = RsvTable{};
+    h_dev_held.assign((size_t)n, 0);
+  }
+};
+
+// DeviceShare GPUs (ks_dev.h)
+struct DevTable {
+  DevPtr<> blob;
+  DevDev dv{};  // (used: view into blob)
+  bool loaded = false;
+  std::vector<uint16_t> h_ids;  // per node: NUMA ids of the device topology (DeviceShare hints)
+  // nodes with device pods placed by ks_assume and not yet ks_unreserve'd: their Unreserve re-derives the
+  // per-instance request from the node's device totals, so ks_update_devices must not change those meanwhile
+  std::vector<int32_t> h_assumed, h_assumed_ckpt;
+  Snap snap[1];  // used
+  void reset(int64_t n) {
+    *this = DevTable{};
+    h_ids.assign((size_t)n, 0);
+  }
+  void checkpoint_host() { h_assumed_ckpt = h_assumed; }
+  void restore_host() { h_assumed = h_assumed_ckpt; }
+};
+
+// NodeNUMAResource cpusets (ks_cpuset.h)
+struct CpuTable {
+  DevPtr<> blob;
+  DevCpu cpu{};
+  bool loaded = false;
+  std::vector<int32_t> cpc;          // CPUsPerCore of each loaded topology
+  std::vector<CpuTopo> h_topos;      // the loaded CPU topologies (ks_update_cpu_state refers to them)
+  std::vector<int8_t> h_topo_dense;
+  std::vector<int8_t> h_nn;          // per node: NUMA nodes of its CPU topology (0 = none, -1 = ids not 0..n-1)
+  Snap snap[1];                      // allocated / excl_pcpu / excl_numa
+  void reset(int64_t n) {
+    *this = CpuTable{};
+    h_nn.assign((size_t)n, 0);
+  }
+};
+
+// NUMA topology policies (ks_numa.h)
+struct NumaTable {
+  DevPtr<> blob;
+  DevNuma nv{};
+  int w = kNumaDev;           // NUMA width of the table and of the kernels (ks_numa.h): kNumaWide once a policy node has
+                              // more than kNumaDev NUMA nodes (numa_install)
+  std::vector<int8_t> h_k;    // per node: NUMA node count of a policy node (0 = no policy / none)
+  Snap snap[1];               // the mutable block {used, off, cs, free, present}
+  Snap free_snap;             // ... its free words alone (numa_refresh_free re-bases them)
+  void reset(int64_t n) {
+    *this = NumaTable{};
+    h_k.assign((size_t)n, 0);
+  }
+};
+
+// preemption (ks_load_node_pods / ks_preempt, ks_preempt.h)
+struct NodePodTable {
+  DevPtr<> blob;                   // the node-pod table (positions sorted per node) + per-call scratch
+  DevNodePods npt{};
+  int32_t slots = 0;               // positions per lane of the dry run (max pods on a node / 64, rounded up)
+  PreemptCand* cand = nullptr;     // [n] (view into blob, as the four below)
+  int32_t* vrank = nullptr;        // [m]
+  uint8_t* status = nullptr;       // [n]
+  PreemptOut* out = nullptr;
+  int32_t* victims = nullptr;      // [kPreemptMaxPods]
+};
+
+// nominated pods (ks_load_nominated, ks_nominated.h): the caller's rows on the host -- the device table is rebuilt
+// whole from them on every change (tens to hundreds of rows) -- and the rows at ks_checkpoint
+struct NomRow {
+  int32_t node, prio;
+  int64_t id;
+  int64_t req[kNomWords];
+};
+struct NomTable {
+  std::vector<NomRow> h_rows, h_ckpt;
+  DevPtr<> blob;                   // the CSR table, then the overlay's output
+  DevNominated nomt{};             // beg == nullptr: no table
+  uint32_t* fit = nullptr;         // [n] nominated_overlay_kernel's Fit reason bits (view into blob)
+  void checkpoint_host() { h_ckpt = h_rows; }
+  // true: the rows changed back, install them (nom_install)
+  bool restore_host() {
+    if (h_rows.empty() && h_ckpt.empty()) return false;
+    h_rows = h_ckpt;
+    return true;
+  }
+};
+
+// PodTopologySpread / InterPodAffinity (ks_topo.h): node columns in the node blob (counters mutable, zone
+// read-only), the normalizing-weight table, the topology step's scratch and one-candidate set
+struct TopoTable {
+  int32_t nkeys = 0, ndom = 1, nprops = 0;
+  std::vector<int32_t*> dom_v;    // [nkeys] column bases (contiguous, stride npad): key k + 1's value index
+  std::vector<int32_t*> count_v;  // [nprops] (contiguous, stride npad, mutable): pods with property p
+  int32_t* dom = nullptr;         // dom_v[0] (view into the node blob)
+  int32_t* count = nullptr;       // count_v[0] (view into the node blob)
+  DevPtr<> blob;                  // everything below is a view into it
+  long long* zsum = nullptr;      // the step's per-domain scratch (ks_topo.h DevTopo)
+  uint32_t *zpres = nullptr, *zsize = nullptr;
+  double* lw = nullptr;
+  int32_t nlw = 0;
+  TopoScratch* scr = nullptr;
+  long long *sraw = nullptr, *iraw = nullptr;  // [npad] per-node raw scores of the step
+  int32_t k = 1;  // topology steps per regular pass (queues of mostly topology pods run several in a row)
+  uint32_t* cchunk = nullptr;
+  uint2* ct = nullptr;
+  int32_t* ccount = nullptr;
+  uint64_t *cbound = nullptr, *ctop = nullptr, *csecond = nullptr;
+};
+
+// the staged batch's flags
+struct StagedFlags {
   int32_t np = 0;
+  bool stale = false;               // a reload dropped the staged batch: ks_schedule_staged is KS_ESTATE until ks_stage_pods
+  bool cpu_bind_required = false;   // the current operation's pods include a required CPU bind policy
+  bool val_bind_required = false;   // ... set by the last successful validate_pods
+  bool bind_required = false;       // ... of the staged batch (ks_stage_pods)
+  bool cpusets_clobbered = false;   // ks_assume reused the batch's cpuset / NUMA buffers since the last schedule
+  // a table the batch was validated against is gone
+  void drop() {
+    stale = stale || np > 0;
+    np = 0;
+  }
+};
+
+struct ks_ctx {
+  ks_config cfg{};
+  Cfg kc{};
+  int device = 0;
+  std::string err;
+  // the stream and the events, ahead of every buffer (destroyed after them)
+  Stream stream;
+  Event pev_sel[kPipeEvents];
+  Event pev_com[kPipeEvents];
+  std::vector<Event> ev_pool;
+  // the tables
+  NodeTable nodes;
+  QuotaTable quota;
+  RsvTable rsv;
+  DevTable dev;
+  CpuTable cpus;
+  NumaTable numa;
+  NodePodTable npods;
+  NomTable nom;
+  TopoTable topo;
+  StagedFlags staged;
+  // fixed-size device objects, allocated once and kept across reloads
+  DevPtr<DevRsv> drv;        // device copy of rsv.rv (kernels read it through a pointer)
+  DevPtr<DevDev> ddv;        // ... of dev.dv
+  DevPtr<DevNuma> dnv;       // ... of numa.nv (always allocated: kernels take its address)
+  DevPtr<RowCol> rowcols;    // [RF_N] device column of each slot-row field
+  DevPtr<DevNodes> dnodes;   // device copy of nodes.d (the hot kernels read column pointers from it)
+  // pods
   PodStage st{};   // staged pods of ks_stage_pods / ks_schedule
   PodStage est{};  // single-pod evaluation (ks_eval_pod)
   PodStage ast{};  // per-pod framework mode (ks_assume / ks_unreserve)
-  int64_t* numa_alloc = nullptr;  // [cpuset_cap][2][numa_w] NUMA-policy allocation per pod of the last call
-  void* evbuf = nullptr;          // ks_eval_pod scratch, kept across calls
+  DevPtr<> evbuf;                 // ks_eval_pod scratch, kept across calls
   size_t evbuf_bytes = 0;
-  void* sumbuf = nullptr;         // ks_eval_pod_summary scratch (sum_buffers), kept across calls like evbuf
+  DevPtr<> sumbuf;                // ks_eval_pod_summary scratch (sum_buffers), kept across calls like evbuf
   size_t sumbuf_bytes = 0;
-  void* sumhost = nullptr;        // ... its pinned host copy: the summary, the top rows, the bitmask words
+  HostPtr sumhost;                // ... its pinned host copy: the summary, the top rows, the bitmask words
   size_t sumhost_bytes = 0;
-  void* ures = nullptr;           // ks_unreserve scratch: node index, the pod's cpuset and NUMA allocation
-  void* rdscratch = nullptr;      // ks_read_nodes: the NodeInfo view of the reservation-restored columns
-  std::vector<int32_t> h_rsv_gi;  // caller reservation row -> CSR position
+  DevPtr<> ures;                  // ks_unreserve scratch: node index, the pod's cpuset and NUMA allocation
+  DevPtr<> dscratch;              // delta uploads (ks_update_*): indices + row words
+  size_t dscratch_bytes = 0;
+  // per-pod outputs of one call (ensure_cpuset_bufs): one allocation, the other four are views into it
+  DevPtr<int2> cpuset_list;              // [pod_cap] (pod, node) of every cpu-bind Reserve
+  int32_t* cpuset_n = nullptr;
+  CpuSet* cpuset_out = nullptr;          // [pod_cap] CPUs allocated per pod of the last schedule
+  uint32_t* cpuset_split = nullptr;      // [cpuset_cap] per pod (CommitArgs.cpuset_split; 8 bytes per pod reserved)
+  int64_t* numa_alloc = nullptr;         // [cpuset_cap][2][numa.w] NUMA-policy allocation per pod of the last call
+  int32_t cpuset_cap = 0;
   // pass scratch
-  uint2* sweep_out = nullptr;
-  uint32_t* cand_chunk = nullptr;
-  uint2* cand_t = nullptr;
-  uint64_t* cand_bound = nullptr;
-  uint64_t* cand_top = nullptr;
-  uint64_t* cand_second = nullptr;
-  void* pre_rsv = nullptr;         // [kMaxBatch][kPreRsvM] reserve_pre_kernel's records (NUMA / device variants)
-  int32_t* cand_total = nullptr;
+  DevPtr<uint32_t> cand_chunk;
+  DevPtr<uint2> cand_t;
+  DevPtr<uint64_t> cand_bound;
+  DevPtr<uint64_t> cand_top;
+  DevPtr<uint64_t> cand_second;
+  DevPtr<> pre_rsv;                // [kMaxBatch][kPreRsvM] reserve_pre_kernel's records (NUMA / device variants)
+  DevPtr<int32_t> cand_total;
+  DevPtr<int32_t> cand_count;
+  DevPtr<int32_t> cursor;
+  DevPtr<unsigned long long> counters;
+  DevPtr<unsigned long long> dev_M;   // [3][64] per pass: normalization maxima (ks_pass.h SweepArgs.dev_M)
+  DevPtr<unsigned long long> dcache;  // [64][npad] DeviceShare phase-0 results (SweepArgs.dcache)
+  int64_t dcache_words = 0;
+  int32_t batch = 64, k = 32;
+  int32_t k_cfg = 32;        // the configured candidates per pod (k: what the commit layout leaves of it, commit_attr_set)
+  CommitPlan plan;           // the commit kernel's variant and LDS image (ks_plan.h): set by commit_attr_set, then only read
+  bool commit_fq = true;     // KS_COMMIT_FQ at ks_create: the dedicated Fit + LoadAware + ElasticQuota commit (ks_fq.h)
+  bool fq_keys = true;       // KS_FQ_KEYS at ks_create: that kernel's slot-key table and evaluator wave
   // node sharding: shard s = rank * vshards + v owns chunks [s*nchunks/S, (s+1)*nchunks/S)
   int32_t nranks = 1, rank = 0, vshards = 1;
   ncclComm_t comm = nullptr;
   struct LoopGroup* loop = nullptr;  // test transport (ks_shard_init_loopback) in place of comm
-  hipEvent_t lev[2][2] = {};         // loopback: [parity][0 = block ready, 1 = peers' blocks pulled]
+  hipEvent_t lev[2][2] = {};         // loopback: [parity][0 = block ready, 1 = peers' blocks pulled] (loop_leave)
   int64_t loop_seq = 0;              // loopback exchanges so far (every rank makes the same sequence)
-  unsigned long long* loop_scratch = nullptr;  // loopback all-reduce: the peers' blocks [nranks][kNormRows * kMaxBatch]
-  unsigned char* gather = nullptr;  // [nranks * vshards] CandSlot blocks
+  DevPtr<unsigned long long> loop_scratch;  // loopback all-reduce: the peers' blocks [nranks][kNormRows * kMaxBatch]
+  DevPtr<unsigned char> gather;      // [nranks * vshards] CandSlot blocks
   size_t gather_bytes = 0;
-  int32_t* cand_count = nullptr;
-  int32_t* cursor = nullptr;
-  unsigned long long* counters = nullptr;
-  int32_t batch = 64, k = 32;
-  RowCol* rowcols = nullptr;  // [RF_N] device column of each slot-row field
-  DevNodes* dnodes = nullptr;  // device copy of d (the hot kernels read column pointers from it)
-  // reservations (ks_rsv.h)
-  void* rsv_blob = nullptr;
-  DevRsv rv{};               // host copy of the device table
-  DevRsv* drv = nullptr;     // device copy (kernels read it through a pointer)
-  bool rsv_based = false;    // node columns hold the base restore of rv
-  int64_t* rsv_allocd_ckpt = nullptr;
-  int32_t* rsv_assigned_ckpt = nullptr;
-  int32_t rsv_ndist = 0;     // distinct order labels
-  int32_t rsv_nrows = 0;     // caller rows (deleted ones included)
-  int32_t rsv_live = 0;      // rows of the device table (the caller rows not deleted)
-  std::vector<int32_t> rsv_perm;  // CSR position -> caller row
-  // host mirror of the caller rows, for ks_add_reservations / ks_delete_reservations (allocated / assigned are
-  // refreshed from the device before each change)
-  struct RsvMirror {
-    std::vector<int32_t> node, assigned;
-    std::vector<uint64_t> cls;
-    std::vector<uint32_t> flags, policy, key_mask;
-    std::vector<int64_t> order, rnz_cpu, rnz_mem;
-    std::vector<int64_t> alloc[kRsvDims], allocd[kRsvDims];
-    std::vector<int64_t> dal, dald;  // [row * KS_DEV_WORDS + w]
-    std::vector<uint8_t> live;
-  } rmir;
-  // DeviceShare GPUs (ks_dev.h)
-  void* dev_blob = nullptr;
-  DevDev dv{};
-  DevDev* ddv = nullptr;
-  bool dev_loaded = false;
-  int64_t* dev_used_ckpt = nullptr;
-  unsigned long long* dev_M = nullptr;  // [3][64] per pass: normalization maxima (ks_pass.h SweepArgs.dev_M)
-  uint64_t soft_union = 0;  // TaintToleration: OR of every node's PreferNoSchedule taint bits (kPodNormDyn at staging)
-  unsigned long long* dcache = nullptr;  // [64][npad] DeviceShare phase-0 results (SweepArgs.dcache)
-  int64_t dcache_words = 0;
-  // NodeNUMAResource cpusets (ks_cpuset.h)
-  void* cpu_blob = nullptr;
-  DevCpu cpu{};
-  bool cpu_loaded = false;
-  std::vector<int32_t> cpu_cpc;          // CPUsPerCore of each loaded topology
-  CpuSet* cpu_ckpt = nullptr;            // allocated / excl_pcpu / excl_numa at ks_checkpoint
-  int2* cpuset_list = nullptr;           // [pod_cap] (pod, node) of every cpu-bind Reserve
-  int32_t* cpuset_n = nullptr;
-  CpuSet* cpuset_out = nullptr;          // [pod_cap] CPUs allocated per pod of the last schedule
-  int32_t cpuset_cap = 0;
-  // NUMA topology policies (ks_numa.h)
-  void* numa_blob = nullptr;
-  DevNuma nv{};
-  int32_t k_cfg = 32;        // the configured candidates per pod (k: what the commit layout leaves of it, commit_attr_set)
-  CommitPlan plan;           // the commit kernel's variant and LDS image (ks_plan.h): set by commit_attr_set, then only read
-  int numa_w = kNumaDev;     // NUMA width of the table and of the kernels (ks_numa.h): kNumaWide once a policy node has
-                             // more than kNumaDev NUMA nodes (numa_install)
-  DevNuma* dnv = nullptr;    // device copy (always allocated: kernels take its address)
-  char* numa_ckpt = nullptr;       // checkpoint copy of the mutable NUMA block (numa_mut_bytes)
-  int64_t numa_policy_nodes = 0;  // nodes with a NUMA topology policy
-  bool cpu_bind_labels = false;   // a node CPU bind policy was loaded (sticky)
-  bool cpu_bind_required = false;    // the current operation's pods include a required CPU bind policy
-  bool val_bind_required = false;    // ... set by the last successful validate_pods
-  bool staged_bind_required = false; // ... of the staged batch (ks_stage_pods)
-  bool staged_stale = false;         // a reload dropped the staged batch: ks_schedule_staged is KS_ESTATE until ks_stage_pods
-  bool cpusets_clobbered = false;    // ks_assume reused the batch's cpuset / NUMA buffers since the last schedule
-  // nodes with device pods placed by ks_assume and not yet ks_unreserve'd: their Unreserve re-derives the
-  // per-instance request from the node's device totals, so ks_update_devices must not change those meanwhile
-  std::vector<int32_t> h_dev_assumed, h_dev_assumed_ckpt;
-  std::vector<int8_t> h_numa_k;    // per node: NUMA node count of a policy node (0 = no policy / none)
-  std::vector<uint16_t> h_dev_ids; // per node: NUMA ids of the device topology (DeviceShare hints)
-  std::vector<uint8_t> h_pol;      // per node: a NUMA topology policy (numa_flags)
-  std::vector<uint8_t> h_dev_held; // per node: a reservation on it holds devices (kDevRsvHeld)
-  bool dev_held_any = false;       // ... on some node (the pass kernels' FEAT bit 16)
-  int64_t* rsv_dald_ckpt = nullptr;  // checkpoint of the reservations' device allocated
-  std::vector<int8_t> h_cpu_nn;    // per node: NUMA nodes of its CPU topology (0 = none, -1 = ids not 0..n-1)
-  std::vector<CpuTopo> h_topos;    // the loaded CPU topologies (ks_update_cpu_state refers to them)
-  std::vector<int8_t> h_topo_dense;
-  std::vector<int32_t> h_rsv_node; // CSR position -> node
-  void* dscratch = nullptr;        // delta uploads (ks_update_*): indices + row words
-  size_t dscratch_bytes = 0;
-  uint32_t* cpuset_split = nullptr;  // [cpuset_cap] per pod (CommitArgs.cpuset_split; 8 bytes per pod reserved)
   // pipelined passes: sweep + select on sstream while the commit runs on stream
   hipStream_t sstream = nullptr;   // shared by the process's contexts on this device (ensure_pipe), never destroyed
   hipStream_t cstream = nullptr;   // the pipelined commits: the CU the sweep stream leaves out (or `stream`)
-  int32_t* pipe = nullptr;          // [0..1] speculative first pod per pass parity, [4..68] commit carry list
-  unsigned long long* pipe_top = nullptr;  // patched passes: [2][64] each pod's top after the list re-evaluation
-  hipEvent_t pev_sel[kPipeEvents] = {};
-  hipEvent_t pev_com[kPipeEvents] = {};
+  DevPtr<int32_t> pipe;             // [0..1] speculative first pod per pass parity, [4..68] commit carry list
+  DevPtr<unsigned long long> pipe_top;  // patched passes: [2][64] each pod's top after the list re-evaluation
   int64_t pipe_k = 0;               // pass index within the current ks_schedule* call
   int32_t pipe_mode = -1;           // ks_set_pipeline (-1: KS_PIPE, default automatic)
-  bool commit_fq = true;            // KS_COMMIT_FQ at ks_create: the dedicated Fit + LoadAware + ElasticQuota commit (ks_fq.h)
-  bool fq_keys = true;              // KS_FQ_KEYS at ks_create: that kernel's slot-key table and evaluator wave
-  // preemption (ks_load_node_pods / ks_preempt, ks_preempt.h)
-  void* npod_blob = nullptr;       // the node-pod table (positions sorted per node) + per-call scratch
-  DevNodePods npt{};
-  int32_t npod_slots = 0;          // positions per lane of the dry run (max pods on a node / 64, rounded up)
-  PreemptCand* pre_cand = nullptr; // [n]
-  int32_t* pre_vrank = nullptr;    // [m]
-  uint8_t* pre_status = nullptr;   // [n]
-  PreemptOut* pre_out = nullptr;
-  int32_t* pre_victims = nullptr;  // [kPreemptMaxPods]
-  // nominated pods (ks_load_nominated, ks_nominated.h): the caller's rows on the host -- the device table is rebuilt
-  // whole from them on every change (tens to hundreds of rows) -- and the rows at ks_checkpoint
-  struct NomRow {
-    int32_t node, prio;
-    int64_t id;
-    int64_t req[kNomWords];
-  };
-  std::vector<NomRow> h_nom, h_nom_ckpt;
-  void* nom_blob = nullptr;        // the CSR table, then the overlay's output
-  DevNominated nomt{};             // beg == nullptr: no table
-  uint32_t* nom_fit = nullptr;     // [n] nominated_overlay_kernel's Fit reason bits
-  // PodTopologySpread / InterPodAffinity (ks_topo.h): node columns in the node blob (counters mutable, zone
-  // read-only), the normalizing-weight table, the topology step's scratch and one-candidate set
-  int32_t topo_nkeys = 0, topo_ndom = 1, topo_nprops = 0;
-  std::vector<int32_t*> topo_dom_v;    // [nkeys] column bases (contiguous, stride npad): key k + 1's value index
-  std::vector<int32_t*> topo_count_v;  // [nprops] (contiguous, stride npad, mutable): pods with property p
-  int32_t* topo_dom = nullptr;         // topo_dom_v[0]
-  int32_t* topo_count = nullptr;       // topo_count_v[0]
-  long long* topo_zsum = nullptr;      // the step's per-domain scratch (ks_topo.h DevTopo)
-  uint32_t *topo_zpres = nullptr, *topo_zsize = nullptr;
-  void* topo_blob = nullptr;
-  double* topo_lw = nullptr;
-  int32_t topo_nlw = 0;
-  TopoScratch* topo_scr = nullptr;
-  long long *topo_sraw = nullptr, *topo_iraw = nullptr;  // [npad] per-node raw scores of the step
-  int32_t topo_k = 1;  // topology steps per regular pass (queues of mostly topology pods run several in a row)
-  uint32_t* topo_cchunk = nullptr;
-  uint2* topo_ct = nullptr;
-  int32_t* topo_ccount = nullptr;
-  uint64_t *topo_cbound = nullptr, *topo_ctop = nullptr, *topo_csecond = nullptr;
+  // the loaded tables' checkpointed device regions, in copy order (the node blob's mutable columns go first,
+  // ks_checkpoint)
+  std::vector<Snap> snaps() const {
+    std::vector<Snap> v;
+    auto add = [&v](bool loaded, const auto& regions) {
+      if (loaded) v.insert(v.end(), std::begin(regions), std::end(regions));
+    };
+    add(quota.blob.get(), quota.snap);
+    add(dev.blob.get(), dev.snap);
+    add(cpus.loaded, cpus.snap);
+    add(numa.blob.get(), numa.snap);
+    add(rsv.blob.get(), rsv.snap);
+    return v;
+  }
   // stats
   ks_stats stats{};
-  std::vector<hipEvent_t> ev_pool;
 };
 
 #define KS_FAIL(ctx, code, ...)                                        \
@@ -1194,22 +1362,36 @@ struct ks_ctx {
 // The entry points whose pods carry no priority refuse a loaded table instead of ignoring it
 #define KS_NOM_REFUSE(ctx, who)                                                                                      \
   do {                                                                                                               \
-    if (!(ctx)->h_nom.empty())                                                                                       \
+    if (!(ctx)->nom.h_rows.empty())                                                                                       \
       KS_FAIL(ctx, KS_EUNSUPPORTED, "%s: a nominated table is loaded (%zu pods) and this entry point carries no pod " \
                                     "priority; use the *_nominated entry points or clear it (ks_load_nominated m = 0)", \
-              who, (ctx)->h_nom.size());                                                                             \
+              who, (ctx)->nom.h_rows.size());                                                                             \
   } while (0)
 
-static int dev_alloc(ks_ctx* ctx, void** p, size_t bytes) {
+// A buffer of `bytes` bytes for p; what p held is freed first.
+template <class T>
+static int dev_alloc(ks_ctx* ctx, DevPtr<T>& p, size_t bytes) {
+  p.reset();
   if (bytes == 0) bytes = 16;
-  hipError_t e = hipMalloc(p, bytes);
+  void* q = nullptr;
+  hipError_t e = hipMalloc(&q, bytes);
   if (e != hipSuccess) KS_FAIL(ctx, KS_ENOMEM, "hipMalloc(%zu) failed: %s", bytes, hipGetErrorString(e));
+  p.reset((T*)q);
   return KS_OK;
 }
 
-static void dev_free(void*& p) {
-  if (p) (void)hipFree(p);
-  p = nullptr;
+static int host_alloc(ks_ctx* ctx, HostPtr& p, size_t bytes) {
+  p.reset();
+  void* q = nullptr;
+  HIPCHK(ctx, hipHostMalloc(&q, bytes, hipHostMallocDefault));
+  p.reset(q);
+  return KS_OK;
+}
+
+// One region into its checkpoint (ks_checkpoint, the installs that seed it) or back (ks_restore)
+static int snap_copy(ks_ctx* ctx, const Snap& s, bool restore) {
+  HIPCHK(ctx, hipMemcpyAsync(restore ? s.live : s.ckpt, restore ? s.ckpt : s.live, s.bytes, hipMemcpyDeviceToDevice, ctx->stream));
+  return KS_OK;
 }
 
 // Leave the loopback group (ks_shard_init_loopback): the group is freed with its last member.
@@ -1232,9 +1414,7 @@ static void loop_leave(ks_ctx* ctx) {
       if (e) (void)hipEventDestroy(e);
       e = nullptr;
     }
-  void* p = ctx->loop_scratch;
-  dev_free(p);
-  ctx->loop_scratch = nullptr;
+  ctx->loop_scratch.reset();
 }
 
 static Cfg make_cfg(const ks_config& c, int nsc) {
@@ -1424,42 +1604,30 @@ int ks_create(const ks_config* cfg, ks_ctx** out) {
   ctx->k = ctx->k_cfg = cfg->candidates > 0 ? std::min(cfg->candidates, kMaxCand) : 32;
   ctx->commit_fq = env_i64("KS_COMMIT_FQ", 1, 0, 1) != 0;  // (per context: a process can build one of each, tests / A-B)
   ctx->fq_keys = env_i64("KS_FQ_KEYS", 1, 0, 1) != 0;
-  if (hipSetDevice(ctx->device) != hipSuccess || hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking) != hipSuccess) {
+  if (hipSetDevice(ctx->device) != hipSuccess || hipStreamCreateWithFlags(&ctx->stream.h, hipStreamNonBlocking) != hipSuccess) {
     g_create_error = "ks_create: cannot create HIP stream";
     delete ctx;
     return KS_EHIP;
   }
-  void* p = nullptr;
   // two sets of candidate lists (CandSet): pipelined passes select pass k+1 while pass k commits
-  size_t cand_bytes = (size_t)2 * kMaxBatch * kMaxCand;
-  if (dev_alloc(ctx, &p, cand_bytes * 4) != KS_OK) goto fail;
-  ctx->cand_chunk = (uint32_t*)p;
-  if (dev_alloc(ctx, &p, cand_bytes * 8) != KS_OK) goto fail;
-  ctx->cand_t = (uint2*)p;
-  if (dev_alloc(ctx, &p, 2 * kMaxBatch * 8) != KS_OK) goto fail;
-  ctx->cand_bound = (uint64_t*)p;
-  if (dev_alloc(ctx, &p, 2 * kMaxBatch * 8) != KS_OK) goto fail;
-  ctx->cand_top = (uint64_t*)p;
-  if (dev_alloc(ctx, &p, 2 * kMaxBatch * 8) != KS_OK) goto fail;
-  ctx->cand_second = (uint64_t*)p;
-  if (dev_alloc(ctx, &p, (size_t)kMaxBatch * kPreRsvM * sizeof(PreRsvT<kNumaWide>)) != KS_OK) goto fail;
-  ctx->pre_rsv = p;
-  if (dev_alloc(ctx, &p, 2 * kMaxBatch * 4) != KS_OK) goto fail;
-  ctx->cand_total = (int32_t*)p;
-  if (dev_alloc(ctx, &p, 2 * kMaxBatch * 4) != KS_OK) goto fail;
-  ctx->cand_count = (int32_t*)p;
-  if (dev_alloc(ctx, &p, 64) != KS_OK) goto fail;
-  ctx->cursor = (int32_t*)p;
-  if (dev_alloc(ctx, &p, 256) != KS_OK) goto fail;
-  ctx->counters = (unsigned long long*)p;
-  if (dev_alloc(ctx, &p, kNormRows * kMaxBatch * 8) != KS_OK) goto fail;
-  ctx->dev_M = (unsigned long long*)p;
+  const size_t cand_bytes = (size_t)2 * kMaxBatch * kMaxCand;
+  if (dev_alloc(ctx, ctx->cand_chunk, cand_bytes * 4) != KS_OK || dev_alloc(ctx, ctx->cand_t, cand_bytes * 8) != KS_OK ||
+      dev_alloc(ctx, ctx->cand_bound, 2 * kMaxBatch * 8) != KS_OK || dev_alloc(ctx, ctx->cand_top, 2 * kMaxBatch * 8) != KS_OK ||
+      dev_alloc(ctx, ctx->cand_second, 2 * kMaxBatch * 8) != KS_OK ||
+      dev_alloc(ctx, ctx->pre_rsv, (size_t)kMaxBatch * kPreRsvM * sizeof(PreRsvT<kNumaWide>)) != KS_OK ||
+      dev_alloc(ctx, ctx->cand_total, 2 * kMaxBatch * 4) != KS_OK || dev_alloc(ctx, ctx->cand_count, 2 * kMaxBatch * 4) != KS_OK ||
+      dev_alloc(ctx, ctx->cursor, 64) != KS_OK || dev_alloc(ctx, ctx->counters, 256) != KS_OK ||
+      dev_alloc(ctx, ctx->dev_M, kNormRows * kMaxBatch * 8) != KS_OK) {
+    g_create_error = ctx->err;
+    ks_destroy(ctx);
+    return KS_ENOMEM;
+  }
   // empty candidate lists until a select writes them: a kernel that reads a list the pass did not write sees no node
   // rather than whatever the allocation held.  KS_TEST_POISON_LISTS=1 (tests only) fills them with large words
   // instead, so a test can check that no kernel reads a list its pass did not write as nodes
-  if (hipMemsetAsync(ctx->cand_count, list_fill(), 2 * kMaxBatch * 4, ctx->stream) != hipSuccess ||
-      hipMemsetAsync(ctx->cand_chunk, list_fill(), cand_bytes * 4, ctx->stream) != hipSuccess ||
-      hipMemsetAsync(ctx->cand_t, list_fill(), cand_bytes * 8, ctx->stream) != hipSuccess ||
+  if (hipMemsetAsync(ctx->cand_count.get(), list_fill(), 2 * kMaxBatch * 4, ctx->stream) != hipSuccess ||
+      hipMemsetAsync(ctx->cand_chunk.get(), list_fill(), cand_bytes * 4, ctx->stream) != hipSuccess ||
+      hipMemsetAsync(ctx->cand_t.get(), list_fill(), cand_bytes * 8, ctx->stream) != hipSuccess ||
       hipStreamSynchronize(ctx->stream) != hipSuccess) {
     g_create_error = "ks_create: cannot clear the candidate lists";
     ks_destroy(ctx);
@@ -1467,10 +1635,6 @@ int ks_create(const ks_config* cfg, ks_ctx** out) {
   }
   *out = ctx;
   return KS_OK;
-fail:
-  g_create_error = ctx->err;
-  ks_destroy(ctx);
-  return KS_ENOMEM;
 }
 
 void ks_destroy(ks_ctx* ctx) {
@@ -1487,72 +1651,15 @@ void ks_destroy(ks_ctx* ctx) {
   for (auto& pr : ctx->lev)
     for (hipEvent_t e : pr)
       if (e) (void)hipEventSynchronize(e);
-  dev_free(ctx->node_blob);
-  dev_free(ctx->ckpt_blob);
-  dev_free(ctx->quota_blob);
-  void* p;
-  dev_free(ctx->st.blob);
-  dev_free(ctx->est.blob);
-  dev_free(ctx->ast.blob);
-  for (PodStage* ps : {&ctx->st, &ctx->est, &ctx->ast})
-    if (ps->h_pack) (void)hipHostFree(ps->h_pack);
-  dev_free(ctx->evbuf);
-  dev_free(ctx->sumbuf);
-  if (ctx->sumhost) (void)hipHostFree(ctx->sumhost);
-  dev_free(ctx->ures);
-  dev_free(ctx->rdscratch);
-  dev_free(ctx->dscratch);
-  p = ctx->sweep_out; dev_free(p);
-  p = ctx->cand_chunk; dev_free(p);
-  p = ctx->cand_t; dev_free(p);
-  p = ctx->cand_bound; dev_free(p);
-  p = ctx->cand_top; dev_free(p);
-  p = ctx->cand_second; dev_free(p);
-  p = ctx->cand_total; dev_free(p);
-  p = ctx->gather; dev_free(p);
   if (ctx->comm) (void)ncclCommDestroy(ctx->comm);
   loop_leave(ctx);
-  p = ctx->cand_count; dev_free(p);
-  p = ctx->cursor; dev_free(p);
-  p = ctx->counters; dev_free(p);
-  p = ctx->rowcols; dev_free(p);
-  p = ctx->dnodes; dev_free(p);
-  p = ctx->drv; dev_free(p);
-  dev_free(ctx->rsv_blob);
-  p = ctx->ddv; dev_free(p);
-  dev_free(ctx->dev_blob);
-  p = ctx->dev_M; dev_free(p);
-  p = ctx->dcache; dev_free(p);
-  dev_free(ctx->cpu_blob);
-  p = ctx->cpuset_list; dev_free(p);
-  dev_free(ctx->numa_blob);
-  p = ctx->dnv; dev_free(p);
-  p = ctx->pipe; dev_free(p);
-  p = ctx->pipe_top; dev_free(p);
-  dev_free(ctx->npod_blob);
-  dev_free(ctx->nom_blob);
-  dev_free(ctx->topo_blob);
-  for (PodStage* ps : {&ctx->st, &ctx->est, &ctx->ast}) {
-    void* t = ps->topo;
-    dev_free(t);
-    t = ps->topo_terms;
-    dev_free(t);
-    t = ps->topo_props;
-    dev_free(t);
-  }
-  for (int i = 0; i < kPipeEvents; ++i) {
-    if (ctx->pev_sel[i]) (void)hipEventDestroy(ctx->pev_sel[i]);
-    if (ctx->pev_com[i]) (void)hipEventDestroy(ctx->pev_com[i]);
-  }
-  for (hipEvent_t e : ctx->ev_pool) (void)hipEventDestroy(e);
-  if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
-  delete ctx;
+  delete ctx;  // the buffers, then the events and the stream (ks_ctx's declaration order)
 }
 
 static void build_col_table(ks_ctx* ctx) {
-  DevNodes& d = ctx->d;
-  ctx->cols.clear();
-  auto add = [&](void* field, int w, bool mut) { ctx->cols.push_back(Col{(void**)field, w, mut}); };
+  DevNodes& d = ctx->nodes.d;
+  ctx->nodes.cols.clear();
+  auto add = [&](void* field, int w, bool mut) { ctx->nodes.cols.push_back(Col{(void**)field, w, mut}); };
   // mutable columns first (contiguous -> one checkpoint copy)
   add(&d.req_cpu, 8, true);
   add(&d.req_mem, 8, true);
@@ -1572,9 +1679,9 @@ static void build_col_table(ks_ctx* ctx) {
   add(&d.cpu_free, 4, true);
   add(&d.cpu_cores, 4, true);
   add(&d.host_ports, 8, true);
-  ctx->topo_count_v.assign((size_t)(ctx->cfg.topology.enable ? ctx->topo_nprops : 0), nullptr);
-  ctx->topo_dom_v.assign((size_t)(ctx->cfg.topology.enable ? ctx->topo_nkeys : 0), nullptr);
-  for (int32_t*& c : ctx->topo_count_v) add(&c, 4, true);
+  ctx->topo.count_v.assign((size_t)(ctx->cfg.topology.enable ? ctx->topo.nprops : 0), nullptr);
+  ctx->topo.dom_v.assign((size_t)(ctx->cfg.topology.enable ? ctx->topo.nkeys : 0), nullptr);
+  for (int32_t*& c : ctx->topo.count_v) add(&c, 4, true);
   // read-only columns
   add(&d.alloc_cpu, 8, false);
   add(&d.alloc_mem, 8, false);
@@ -1600,7 +1707,7 @@ static void build_col_table(ks_ctx* ctx) {
   add(&d.taints_hard, 8, false);
   add(&d.taints_soft, 8, false);
   add(&d.labels, 8, false);
-  for (int32_t*& c : ctx->topo_dom_v) add(&c, 4, false);
+  for (int32_t*& c : ctx->topo.dom_v) add(&c, 4, false);
 }
 
 // host source pointers in the same order as build_col_table (NULL = zeros); n = the rows of c
@@ -1624,7 +1731,7 @@ static std::vector<const void*> host_cols(const ks_ctx* ctx, const ks_node_cols*
   v.push_back(nullptr);  // cpu_free: ks_load_cpu_state (-1 = no CPU topology)
   v.push_back(nullptr);  // cpu_cores: cores_refresh
   v.push_back(c->host_ports);
-  for (size_t q = 0; q < ctx->topo_count_v.size(); ++q) v.push_back(c->topo_count ? c->topo_count + (int64_t)q * n : nullptr);
+  for (size_t q = 0; q < ctx->topo.count_v.size(); ++q) v.push_back(c->topo_count ? c->topo_count + (int64_t)q * n : nullptr);
   v.push_back(c->alloc_milli_cpu);
   v.push_back(c->alloc_memory);
   v.push_back(c->alloc_ephemeral);
@@ -1650,7 +1757,7 @@ static std::vector<const void*> host_cols(const ks_ctx* ctx, const ks_node_cols*
   v.push_back(c->taints_soft);
   v.push_back(c->labels);
   // (NULL: -1, set after the copy)
-  for (size_t k = 0; k < ctx->topo_dom_v.size(); ++k) v.push_back(c->topo_domain ? c->topo_domain + (int64_t)k * n : nullptr);
+  for (size_t k = 0; k < ctx->topo.dom_v.size(); ++k) v.push_back(c->topo_domain ? c->topo_domain + (int64_t)k * n : nullptr);
   return v;
 }
 
@@ -1713,7 +1820,7 @@ static int validate_nodes(ks_ctx* ctx, const ks_node_cols* c, int64_t n) {
 
 // Device table of the slot-row fields' columns (RowField order), read by the commit kernel.
 static int upload_rowcols(ks_ctx* ctx) {
-  const DevNodes& d = ctx->d;
+  const DevNodes& d = ctx->nodes.d;
   RowCol h[RF_N] = {};
   auto set = [&](int f, const void* p, int w) { h[f].p = p; h[f].width = w; };
   set(RF_REQ_CPU, d.req_cpu, 8);
@@ -1736,39 +1843,29 @@ static int upload_rowcols(ks_ctx* ctx) {
   set(RF_ALLOWED, d.allowed_pods, 4);
   set(RF_LA_BITS, d.la_bits, 4);
   set(RF_RSV_CLS, d.rsv_cls, 8);
-  set(RF_RSV_BEG, ctx->rv.beg ? (const void*)ctx->rv.beg : (const void*)d.la_bits, 4);
-  set(RF_RSV_END, ctx->rv.beg ? (const void*)(ctx->rv.beg + 1) : (const void*)d.la_bits, 4);
+  set(RF_RSV_BEG, ctx->rsv.rv.beg ? (const void*)ctx->rsv.rv.beg : (const void*)d.la_bits, 4);
+  set(RF_RSV_END, ctx->rsv.rv.beg ? (const void*)(ctx->rsv.rv.beg + 1) : (const void*)d.la_bits, 4);
   set(RF_NUMA_A, d.numa_amilli, 8);
   set(RF_NUMA_OFF, d.numa_off, 8);
   set(RF_NUMA_RATIO, d.numa_ratio, 8);
   set(RF_CPU_FREE, d.cpu_free, 4);
-  if (!ctx->rowcols) {
-    void* p = nullptr;
-    if (dev_alloc(ctx, &p, sizeof(h)) != KS_OK) return KS_ENOMEM;
-    ctx->rowcols = (RowCol*)p;
+  if (!ctx->rowcols.get() && dev_alloc(ctx, ctx->rowcols, sizeof(h)) != KS_OK) return KS_ENOMEM;
+  if (!ctx->dnodes.get() && dev_alloc(ctx, ctx->dnodes, sizeof(DevNodes)) != KS_OK) return KS_ENOMEM;
+  if (!ctx->dnv.get()) {
+    if (dev_alloc(ctx, ctx->dnv, sizeof(DevNuma)) != KS_OK) return KS_ENOMEM;
+    HIPCHK(ctx, hipMemsetAsync(ctx->dnv.get(), 0, sizeof(DevNuma), ctx->stream));
   }
-  if (!ctx->dnodes) {
-    void* p = nullptr;
-    if (dev_alloc(ctx, &p, sizeof(DevNodes)) != KS_OK) return KS_ENOMEM;
-    ctx->dnodes = (DevNodes*)p;
-  }
-  if (!ctx->dnv) {
-    void* p = nullptr;
-    if (dev_alloc(ctx, &p, sizeof(DevNuma)) != KS_OK) return KS_ENOMEM;
-    HIPCHK(ctx, hipMemsetAsync(p, 0, sizeof(DevNuma), ctx->stream));
-    ctx->dnv = (DevNuma*)p;
-  }
-  HIPCHK(ctx, hipMemcpyAsync(ctx->rowcols, h, sizeof(h), hipMemcpyHostToDevice, ctx->stream));
-  HIPCHK(ctx, hipMemcpyAsync(ctx->dnodes, &ctx->d, sizeof(DevNodes), hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(ctx, hipMemcpyAsync(ctx->rowcols.get(), h, sizeof(h), hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(ctx, hipMemcpyAsync(ctx->dnodes.get(), &ctx->nodes.d, sizeof(DevNodes), hipMemcpyHostToDevice, ctx->stream));
   HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
   return KS_OK;
 }
 
 static int upload_prep_nodes(ks_ctx* ctx) {
   const int threads = 256;
-  const int blocks = (int)((ctx->n + threads - 1) / threads);
+  const int blocks = (int)((ctx->nodes.n + threads - 1) / threads);
   if (blocks > 0)
-    hipLaunchKernelGGL(prep_nodes_kernel, dim3(blocks), dim3(threads), 0, ctx->stream, ctx->d, ctx->n,
+    hipLaunchKernelGGL(prep_nodes_kernel, dim3(blocks), dim3(threads), 0, ctx->stream, ctx->nodes.d, ctx->nodes.n,
                        ctx->cfg.loadaware.filter_expired_node_metrics);
   HIPCHK(ctx, hipGetLastError());
   return KS_OK;
@@ -1777,13 +1874,13 @@ static int upload_prep_nodes(ks_ctx* ctx) {
 // CoresWord of every node (ks_device.h) after a load or delta of the node rows or the CPU state; the schedule
 // passes keep it current themselves (cpuset_kernel), as does ks_unreserve.
 // the NUMA-node words cpuset_kernel refreshes (DevNuma.free), or none without a NUMA-node table
-static int32_t* numa_words(const ks_ctx* ctx) { return (ctx->numa_blob && ctx->kc.numa_pol) ? ctx->nv.free : nullptr; }
+static int32_t* numa_words(const ks_ctx* ctx) { return (ctx->numa.blob.get() && ctx->kc.numa_pol) ? ctx->numa.nv.free : nullptr; }
 
 static int cores_refresh(ks_ctx* ctx) {
-  if (!ctx->cfg.numa.enable || ctx->n == 0) return KS_OK;
-  hipLaunchKernelGGL(cores_kernel, dim3((unsigned)((ctx->n + 255) / 256)), dim3(256), 0, ctx->stream, ctx->cpu,
-                     (int32_t)ctx->cpu_loaded, (const uint32_t*)ctx->d.numa_flags, ctx->d.cpu_cores, (const int32_t*)nullptr,
-                     ctx->n);
+  if (!ctx->cfg.numa.enable || ctx->nodes.n == 0) return KS_OK;
+  hipLaunchKernelGGL(cores_kernel, dim3((unsigned)((ctx->nodes.n + 255) / 256)), dim3(256), 0, ctx->stream, ctx->cpus.cpu,
+                     (int32_t)ctx->cpus.loaded, (const uint32_t*)ctx->nodes.d.numa_flags, ctx->nodes.d.cpu_cores, (const int32_t*)nullptr,
+                     ctx->nodes.n);
   HIPCHK(ctx, hipGetLastError());
   return KS_OK;
 }
@@ -1791,7 +1888,7 @@ static int cores_refresh(ks_ctx* ctx) {
 // Cfg.cores: the per-node core counts take part in the Filter once a node CPU bind policy or a required pod policy
 // has been seen; the passes then choose CPU ids after every commit (cpuset_kernel) so that the counts stay exact.
 static void cores_mode(ks_ctx* ctx) {
-  ctx->kc.cores = (ctx->cfg.numa.enable && (ctx->cpu_bind_labels || ctx->cpu_bind_required)) ? 1 : 0;
+  ctx->kc.cores = (ctx->cfg.numa.enable && (ctx->nodes.cpu_bind_labels || ctx->staged.cpu_bind_required)) ? 1 : 0;
 }
 
 static int rsv_install(ks_ctx* ctx, const ks_reservation_cols* rc, int32_t nr, const int32_t* caller = nullptr,
@@ -1804,61 +1901,60 @@ static int numa_refresh_free(ks_ctx* ctx);
 // PodTopologySpread / InterPodAffinity: the topologyNormalizingWeight table log(s + 2) for every topology size a
 // pod can see (s <= nodes; the host's libm, as the oracle), the topology step's scratch and one-candidate set
 static int topo_install(ks_ctx* ctx) {
-  dev_free(ctx->topo_blob);
   // sizes a pod can see: the hostname's up to n nodes, another key's up to ndom values + ""
-  const int32_t nlw = (int32_t)std::max<int64_t>(ctx->n, ctx->topo_ndom + 1) + 2;
+  const int32_t nlw = (int32_t)std::max<int64_t>(ctx->nodes.n, ctx->topo.ndom + 1) + 2;
   const size_t b_lw = ((size_t)nlw * 8 + 255) / 256 * 256;
   const size_t b_scr = (sizeof(TopoScratch) + 255) / 256 * 256;
   const size_t b_cand = (size_t)kMaxBatch * kMaxCand * (4 + 8) + (size_t)kMaxBatch * (4 + 8 * 3);
-  const size_t b_raw = (size_t)ctx->npad * 8 * 2;
-  const size_t nw = ((size_t)ctx->topo_ndom + 31) / 32;
-  const size_t b_zsum = (size_t)kTopoTerms * (size_t)ctx->topo_ndom * 8, b_bits = (size_t)kTopoTerms * nw * 4;
+  const size_t b_raw = (size_t)ctx->nodes.npad * 8 * 2;
+  const size_t nw = ((size_t)ctx->topo.ndom + 31) / 32;
+  const size_t b_zsum = (size_t)kTopoTerms * (size_t)ctx->topo.ndom * 8, b_bits = (size_t)kTopoTerms * nw * 4;
   const size_t tot = b_lw + b_scr + b_cand + b_raw + b_zsum + 2 * b_bits;
-  if (dev_alloc(ctx, &ctx->topo_blob, tot) != KS_OK) return KS_ENOMEM;
-  char* b = (char*)ctx->topo_blob;
+  if (dev_alloc(ctx, ctx->topo.blob, tot) != KS_OK) return KS_ENOMEM;
+  char* b = (char*)ctx->topo.blob.get();
   HIPCHK(ctx, hipMemsetAsync(b, 0, tot, ctx->stream));
-  ctx->topo_sraw = (long long*)(b + b_lw + b_scr + b_cand);
-  ctx->topo_iraw = ctx->topo_sraw + ctx->npad;
-  ctx->topo_zsum = (long long*)(b + b_lw + b_scr + b_cand + b_raw);
-  ctx->topo_zpres = (uint32_t*)(b + b_lw + b_scr + b_cand + b_raw + b_zsum);
-  ctx->topo_zsize = (uint32_t*)(b + b_lw + b_scr + b_cand + b_raw + b_zsum + b_bits);
-  ctx->topo_lw = (double*)b;
-  ctx->topo_nlw = nlw;
-  ctx->topo_scr = (TopoScratch*)(b + b_lw);
+  ctx->topo.sraw = (long long*)(b + b_lw + b_scr + b_cand);
+  ctx->topo.iraw = ctx->topo.sraw + ctx->nodes.npad;
+  ctx->topo.zsum = (long long*)(b + b_lw + b_scr + b_cand + b_raw);
+  ctx->topo.zpres = (uint32_t*)(b + b_lw + b_scr + b_cand + b_raw + b_zsum);
+  ctx->topo.zsize = (uint32_t*)(b + b_lw + b_scr + b_cand + b_raw + b_zsum + b_bits);
+  ctx->topo.lw = (double*)b;
+  ctx->topo.nlw = nlw;
+  ctx->topo.scr = (TopoScratch*)(b + b_lw);
   char* c = b + b_lw + b_scr;
-  ctx->topo_ct = (uint2*)c;
+  ctx->topo.ct = (uint2*)c;
   c += (size_t)kMaxBatch * kMaxCand * 8;
-  ctx->topo_cbound = (uint64_t*)c;
+  ctx->topo.cbound = (uint64_t*)c;
   c += kMaxBatch * 8;
-  ctx->topo_ctop = (uint64_t*)c;
+  ctx->topo.ctop = (uint64_t*)c;
   c += kMaxBatch * 8;
-  ctx->topo_csecond = (uint64_t*)c;
+  ctx->topo.csecond = (uint64_t*)c;
   c += kMaxBatch * 8;
-  ctx->topo_cchunk = (uint32_t*)c;
+  ctx->topo.cchunk = (uint32_t*)c;
   c += (size_t)kMaxBatch * kMaxCand * 4;
-  ctx->topo_ccount = (int32_t*)c;
+  ctx->topo.ccount = (int32_t*)c;
   std::vector<double> lw((size_t)nlw);
   for (int32_t i = 0; i < nlw; ++i) lw[(size_t)i] = log((double)(i + 2));
-  HIPCHK(ctx, hipMemcpyAsync(ctx->topo_lw, lw.data(), (size_t)nlw * 8, hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(ctx, hipMemcpyAsync(ctx->topo.lw, lw.data(), (size_t)nlw * 8, hipMemcpyHostToDevice, ctx->stream));
   const TopoScratch init = topo_scratch_init();
-  HIPCHK(ctx, hipMemcpyAsync(ctx->topo_scr, &init, sizeof(init), hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(ctx, hipMemcpyAsync(ctx->topo.scr, &init, sizeof(init), hipMemcpyHostToDevice, ctx->stream));
   HIPCHK(ctx, hipStreamSynchronize(ctx->stream));  // (pageable source)
   return KS_OK;
 }
 
 static DevTopo dev_topo(const ks_ctx* ctx) {
   DevTopo t;
-  t.dom = ctx->topo_dom;
-  t.count = ctx->topo_count;
-  t.npad = ctx->npad;
-  t.nkeys = ctx->topo_nkeys;
-  t.ndom = ctx->topo_ndom;
-  t.lw = ctx->topo_lw;
-  t.nlw = ctx->topo_nlw;
-  t.nw = (ctx->topo_ndom + 31) / 32;
-  t.zsum = ctx->topo_zsum;
-  t.zpres = ctx->topo_zpres;
-  t.zsize = ctx->topo_zsize;
+  t.dom = ctx->topo.dom;
+  t.count = ctx->topo.count;
+  t.npad = ctx->nodes.npad;
+  t.nkeys = ctx->topo.nkeys;
+  t.ndom = ctx->topo.ndom;
+  t.lw = ctx->topo.lw;
+  t.nlw = ctx->topo.nlw;
+  t.nw = (ctx->topo.ndom + 31) / 32;
+  t.zsum = ctx->topo.zsum;
+  t.zpres = ctx->topo.zpres;
+  t.zsize = ctx->topo.zsize;
   return t;
 }
 
@@ -1867,69 +1963,27 @@ int ks_load_nodes(ks_ctx* ctx, const ks_node_cols* nodes, int64_t n) {
   if (int rc = validate_nodes(ctx, nodes, n); rc != KS_OK) return rc;
   HIPCHK(ctx, hipSetDevice(ctx->device));
   HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-  ctx->h_dev_assumed.clear();
-  dev_free(ctx->node_blob);
-  dev_free(ctx->ckpt_blob);
-  void* p = ctx->sweep_out;
-  dev_free(p);
-  ctx->sweep_out = nullptr;
-  ctx->rsv_based = false;  // fresh columns (a loaded reservation table is dropped: reload it)
-  ctx->rsv_nrows = 0;
-  ctx->rsv_live = 0;
-  ctx->rmir = ks_ctx::RsvMirror{};
-  ctx->h_rsv_gi.clear();
-  ctx->h_rsv_node.clear();
-  ctx->rsv_perm.clear();
-  ctx->h_dev_held.assign((size_t)n, 0);  // ... and with it what its rows held: no node's devices are held
-  ctx->dev_held_any = false;
-  // the other tables indexed by node go with the old nodes (include/koordgpu.h "Reusing a context"): the device
-  // table, the CPU state and the NUMA-node table with its width, and the per-node host caches derived from them, at
-  // the new node count before the first helper below indexes them (dev_apply_held, check_dev_numa, numa_refresh_free)
-  dev_free(ctx->dev_blob);
-  ctx->dv = DevDev{};
-  ctx->dev_used_ckpt = nullptr;
-  ctx->dev_loaded = false;
-  ctx->h_dev_ids.assign((size_t)n, 0);
-  ctx->h_dev_assumed_ckpt.clear();
-  dev_free(ctx->cpu_blob);
-  ctx->cpu = DevCpu{};
-  ctx->cpu_ckpt = nullptr;
-  ctx->cpu_loaded = false;
-  ctx->cpu_cpc.clear();
-  ctx->h_topos.clear();
-  ctx->h_topo_dense.clear();
-  ctx->h_cpu_nn.assign((size_t)n, 0);
-  dev_free(ctx->numa_blob);
-  ctx->nv = DevNuma{};
-  ctx->numa_ckpt = nullptr;
-  ctx->numa_w = kNumaDev;
-  ctx->numa_policy_nodes = 0;
-  ctx->h_numa_k.assign((size_t)n, 0);
-  // scratch sized by the old padded node count, allocated again on demand
-  dev_free(ctx->rdscratch);
+  // The old nodes go, and with them every table indexed by node (include/koordgpu.h "Reusing a context"): a loaded
+  // reservation table (reload it) and what its rows held, the device table, the CPU state, the NUMA-node table with
+  // its width, the node-pod table (ks_preempt is KS_ESTATE until ks_load_node_pods) and the nominated table with its
+  // checkpoint.  The order is a contract: the device blob is freed before rsv_install(nullptr, 0) below runs
+  // dev_apply_held, and the per-node host caches are at the new node count before the first helper below indexes
+  // them (dev_apply_held, check_dev_numa, numa_refresh_free).  The quota table is not indexed by node and stays.
+  ctx->nodes = {};
+  ctx->rsv.reset(n);
+  ctx->dev.reset(n);
+  ctx->cpus.reset(n);
+  ctx->numa.reset(n);
   // a staged batch was validated and flagged (kPodNormDyn, the scalar width) against the old nodes, and the last
   // call's results, cpusets and NUMA allocations belong to them: ks_schedule_staged refuses until ks_stage_pods
-  ctx->staged_stale = ctx->staged_stale || ctx->np > 0;
-  ctx->np = 0;
-  // the node-pod table (ks_load_node_pods) is indexed by the old node rows and its per-call scratch is sized to the
-  // old node count: drop it, so ks_preempt returns KS_ESTATE until it is reloaded for these nodes
-  dev_free(ctx->npod_blob);
-  // ... and the nominated table with its checkpoint: its rows name the old node rows (reload it for these nodes)
-  dev_free(ctx->nom_blob);
-  ctx->nomt = DevNominated{};
-  ctx->nom_fit = nullptr;
-  ctx->h_nom.clear();
-  ctx->h_nom_ckpt.clear();
-  ctx->npt = DevNodePods{};
-  ctx->pre_cand = nullptr;
-  ctx->pre_vrank = nullptr;
-  ctx->pre_status = nullptr;
-  ctx->pre_out = nullptr;
-  ctx->pre_victims = nullptr;
-  ctx->n = n;
-  ctx->nchunks = (n + 63) / 64;
-  if (ctx->nchunks == 0) ctx->nchunks = 1;
-  ctx->npad = ctx->nchunks * 64;
+  ctx->staged.drop();
+  ctx->npods = {};
+  ctx->nom = {};
+  ctx->topo = {};
+  ctx->nodes.n = n;
+  ctx->nodes.nchunks = (n + 63) / 64;
+  if (ctx->nodes.nchunks == 0) ctx->nodes.nchunks = 1;
+  ctx->nodes.npad = ctx->nodes.nchunks * 64;
   int nsc = 0;
   for (int k = 0; k < KS_MAX_SCALARS; ++k) {
     bool used = ctx->cfg.fit.weight_scalar[k] != 0;
@@ -1937,65 +1991,60 @@ int ks_load_nodes(ks_ctx* ctx, const ks_node_cols* nodes, int64_t n) {
     for (int64_t i = 0; !used && nodes->req_scalar[k] && i < n; ++i) used = nodes->req_scalar[k][i] != 0;
     if (used) nsc = k + 1;
   }
-  ctx->nsc = nsc <= 0 ? 0 : (nsc <= 2 ? 2 : 4);
-  ctx->kc = make_cfg(ctx->cfg, ctx->nsc);
-  ctx->soft_union = 0;
-  for (int64_t i = 0; nodes->taints_soft && i < n; ++i) ctx->soft_union |= nodes->taints_soft[i];
-  ctx->topo_nkeys = ctx->cfg.topology.enable ? nodes->topo_nkeys : 0;
-  ctx->topo_ndom = ctx->cfg.topology.enable ? nodes->topo_ndomains : 1;
-  ctx->topo_nprops = ctx->cfg.topology.enable ? nodes->topo_nprops : 0;
+  ctx->nodes.nsc = nsc <= 0 ? 0 : (nsc <= 2 ? 2 : 4);
+  ctx->kc = make_cfg(ctx->cfg, ctx->nodes.nsc);
+  for (int64_t i = 0; nodes->taints_soft && i < n; ++i) ctx->nodes.soft_union |= nodes->taints_soft[i];
+  ctx->topo.nkeys = ctx->cfg.topology.enable ? nodes->topo_nkeys : 0;
+  ctx->topo.ndom = ctx->cfg.topology.enable ? nodes->topo_ndomains : 1;
+  ctx->topo.nprops = ctx->cfg.topology.enable ? nodes->topo_nprops : 0;
   build_col_table(ctx);
   size_t total = 0, mut = 0;
-  for (const Col& c : ctx->cols) {
-    total += (size_t)ctx->npad * c.width;
-    if (c.mutable_) mut += (size_t)ctx->npad * c.width;
+  for (const Col& c : ctx->nodes.cols) {
+    total += (size_t)ctx->nodes.npad * c.width;
+    if (c.mutable_) mut += (size_t)ctx->nodes.npad * c.width;
   }
-  ctx->mut_bytes = mut;
-  if (dev_alloc(ctx, &ctx->node_blob, total) != KS_OK) return KS_ENOMEM;
-  HIPCHK(ctx, hipMemsetAsync(ctx->node_blob, 0, total, ctx->stream));
-  char* base = (char*)ctx->node_blob;
+  ctx->nodes.mut_bytes = mut;
+  if (dev_alloc(ctx, ctx->nodes.blob, total) != KS_OK) return KS_ENOMEM;
+  HIPCHK(ctx, hipMemsetAsync(ctx->nodes.blob.get(), 0, total, ctx->stream));
+  char* base = (char*)ctx->nodes.blob.get();
   std::vector<const void*> src = host_cols(ctx, nodes, n);
-  for (size_t i = 0; i < ctx->cols.size(); ++i) {
-    *ctx->cols[i].dev = base;
+  for (size_t i = 0; i < ctx->nodes.cols.size(); ++i) {
+    *ctx->nodes.cols[i].dev = base;
     if (src[i] && n > 0)
-      HIPCHK(ctx, hipMemcpyAsync(base, src[i], (size_t)n * ctx->cols[i].width, hipMemcpyHostToDevice, ctx->stream));
-    base += (size_t)ctx->npad * ctx->cols[i].width;
+      HIPCHK(ctx, hipMemcpyAsync(base, src[i], (size_t)n * ctx->nodes.cols[i].width, hipMemcpyHostToDevice, ctx->stream));
+    base += (size_t)ctx->nodes.npad * ctx->nodes.cols[i].width;
   }
-  HIPCHK(ctx, hipMemsetAsync(ctx->d.cpu_free, 0xFF, (size_t)ctx->npad * 4, ctx->stream));  // no CPU topology yet
+  HIPCHK(ctx, hipMemsetAsync(ctx->nodes.d.cpu_free, 0xFF, (size_t)ctx->nodes.npad * 4, ctx->stream));  // no CPU topology yet
   if (ctx->cfg.topology.enable) {
-    ctx->topo_dom = ctx->topo_dom_v.empty() ? nullptr : ctx->topo_dom_v[0];
-    ctx->topo_count = ctx->topo_count_v.empty() ? nullptr : ctx->topo_count_v[0];
-    if (!nodes->topo_domain && ctx->topo_dom)
-      HIPCHK(ctx, hipMemsetAsync(ctx->topo_dom, 0xFF, (size_t)ctx->npad * 4 * ctx->topo_nkeys, ctx->stream));
+    ctx->topo.dom = ctx->topo.dom_v.empty() ? nullptr : ctx->topo.dom_v[0];
+    ctx->topo.count = ctx->topo.count_v.empty() ? nullptr : ctx->topo.count_v[0];
+    if (!nodes->topo_domain && ctx->topo.dom)
+      HIPCHK(ctx, hipMemsetAsync(ctx->topo.dom, 0xFF, (size_t)ctx->nodes.npad * 4 * ctx->topo.nkeys, ctx->stream));
     if (topo_install(ctx) != KS_OK) return KS_ENOMEM;
   }
-  ctx->cpu_loaded = false;
   // two sweep outputs: patched pipelined passes sweep pass k+1 while pass k's re-sweep still reads pass k's
-  if (dev_alloc(ctx, &p, (size_t)2 * ctx->nchunks * 64 * 8) != KS_OK) return KS_ENOMEM;
-  ctx->sweep_out = (uint2*)p;
+  if (dev_alloc(ctx, ctx->nodes.sweep_out, (size_t)2 * ctx->nodes.nchunks * 64 * 8) != KS_OK) return KS_ENOMEM;
   if (upload_rowcols(ctx) != KS_OK) return KS_ENOMEM;
   if (upload_prep_nodes(ctx) != KS_OK) return KS_EHIP;
   if (ctx->cfg.reservation.enable && rsv_install(ctx, nullptr, 0) != KS_OK) return KS_EHIP;
   if (ctx->cfg.deviceshare.enable && dev_install(ctx, nullptr) != KS_OK) return KS_EHIP;
   // NUMA topology policies: an empty NUMA-node table until ks_load_numa_nodes
-  ctx->numa_policy_nodes = 0;
-  ctx->cpu_bind_labels = false;
-  ctx->h_pol.assign((size_t)n, 0);
+  ctx->nodes.h_pol.assign((size_t)n, 0);
   for (int64_t i = 0; ctx->cfg.numa.enable && nodes->numa_flags && i < n; ++i) {
-    ctx->h_pol[(size_t)i] = ((nodes->numa_flags[i] >> KS_NUMA_POLICY_SHIFT) & 3u) != 0;
-    ctx->numa_policy_nodes += ((nodes->numa_flags[i] >> KS_NUMA_POLICY_SHIFT) & 3u) != 0;
-    ctx->cpu_bind_labels |= ((nodes->numa_flags[i] >> KS_NUMA_CPU_BIND_SHIFT) & 3u) != 0;
+    ctx->nodes.h_pol[(size_t)i] = ((nodes->numa_flags[i] >> KS_NUMA_POLICY_SHIFT) & 3u) != 0;
+    ctx->nodes.numa_policy_nodes += ((nodes->numa_flags[i] >> KS_NUMA_POLICY_SHIFT) & 3u) != 0;
+    ctx->nodes.cpu_bind_labels |= ((nodes->numa_flags[i] >> KS_NUMA_CPU_BIND_SHIFT) & 3u) != 0;
   }
   cores_mode(ctx);
   if (cores_refresh(ctx) != KS_OK) return KS_EHIP;
-  if (ctx->numa_policy_nodes > 0) {
+  if (ctx->nodes.numa_policy_nodes > 0) {
     if (numa_install(ctx, nullptr, nullptr, nullptr) != KS_OK) return KS_EHIP;
     ctx->kc.numa_pol = 1;
     ctx->kc.monotone = 0;  // a Reserve can move a node's best NUMA hint: keys are not monotone
     ctx->kc.monotone_nd = 0;
   } else {
     // no policy node: the device copy describes no table either (not the dropped one's freed columns)
-    HIPCHK(ctx, hipMemcpyAsync(ctx->dnv, &ctx->nv, sizeof(DevNuma), hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(ctx->dnv.get(), &ctx->numa.nv, sizeof(DevNuma), hipMemcpyHostToDevice, ctx->stream));
   }
   HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
   return KS_OK;
@@ -2009,21 +2058,21 @@ __global__ void dev_held_kernel(uint32_t* flags, const uint8_t* held, int64_t n)
 }
 
 static int dev_apply_held(ks_ctx* ctx) {
-  ctx->dev_held_any = false;
-  if (!ctx->dev_blob || ctx->n == 0) return KS_OK;
-  if (ctx->h_dev_held.size() != (size_t)ctx->n) ctx->h_dev_held.assign((size_t)ctx->n, 0);
-  for (uint8_t h : ctx->h_dev_held) ctx->dev_held_any = ctx->dev_held_any || h != 0;
-  void* p = nullptr;
-  if (dev_alloc(ctx, &p, (size_t)ctx->n) != KS_OK) return KS_ENOMEM;
-  HIPCHK(ctx, hipMemcpyAsync(p, ctx->h_dev_held.data(), (size_t)ctx->n, hipMemcpyHostToDevice, ctx->stream));
-  hipLaunchKernelGGL(dev_held_kernel, dim3((unsigned)((ctx->n + 255) / 256)), dim3(256), 0, ctx->stream,
-                     const_cast<uint32_t*>(ctx->dv.flags), (const uint8_t*)p, ctx->n);
+  ctx->rsv.dev_held_any = false;
+  if (!ctx->dev.blob.get() || ctx->nodes.n == 0) return KS_OK;
+  if (ctx->rsv.h_dev_held.size() != (size_t)ctx->nodes.n) ctx->rsv.h_dev_held.assign((size_t)ctx->nodes.n, 0);
+  for (uint8_t h : ctx->rsv.h_dev_held) ctx->rsv.dev_held_any = ctx->rsv.dev_held_any || h != 0;
+  DevPtr<uint8_t> p;
+  if (dev_alloc(ctx, p, (size_t)ctx->nodes.n) != KS_OK) return KS_ENOMEM;
+  HIPCHK(ctx, hipMemcpyAsync(p.get(), ctx->rsv.h_dev_held.data(), (size_t)ctx->nodes.n, hipMemcpyHostToDevice, ctx->stream));
+  hipLaunchKernelGGL(dev_held_kernel, dim3((unsigned)((ctx->nodes.n + 255) / 256)), dim3(256), 0, ctx->stream,
+                     const_cast<uint32_t*>(ctx->dev.dv.flags), (const uint8_t*)p.get(), ctx->nodes.n);
   HIPCHK(ctx, hipGetLastError());
   HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-  dev_free(p);
+  p.reset();
   // the plugin set with reservations holding devices (FEAT 31) is not built at NUMA width 8 (csrc/Makefile WFEATS):
   // refused here, at the load that completes the combination, not at the first schedule
-  if (ctx->numa_w == kNumaWide && ctx->kc.rsv && ctx->kc.dev && ctx->dev_held_any)
+  if (ctx->numa.w == kNumaWide && ctx->kc.rsv && ctx->kc.dev && ctx->rsv.dev_held_any)
     KS_FAIL(ctx, KS_EUNSUPPORTED,
             "reservations holding devices together with a NUMA-policy node with more than %d NUMA nodes", kNumaDev);
   return KS_OK;
@@ -2031,7 +2080,7 @@ static int dev_apply_held(ks_ctx* ctx) {
 
 static int rsv_launch_base(ks_ctx* ctx, const int32_t* didx, int64_t count, int64_t sign, int32_t classes) {
   if (count <= 0) return KS_OK;
-  hipLaunchKernelGGL(rsv_base_kernel, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, ctx->stream, ctx->d, ctx->rv,
+  hipLaunchKernelGGL(rsv_base_kernel, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, ctx->stream, ctx->nodes.d, ctx->rsv.rv,
                      didx, count, sign, classes);
   HIPCHK(ctx, hipGetLastError());
   return KS_OK;
@@ -2047,7 +2096,7 @@ static int rsv_install(ks_ctx* ctx, const ks_reservation_cols* rc, int32_t nr, c
   if (nr > 0 && (!rc || !rc->node || !rc->owner_classes || !rc->key_mask))
     KS_FAIL(ctx, KS_EINVAL, "ks_reservation_cols: node, owner_classes and key_mask are required");
   for (int32_t r = 0; r < nr; ++r) {
-    if (rc->node[r] < 0 || rc->node[r] >= ctx->n) KS_FAIL(ctx, KS_EINVAL, "reservation %d: node %d out of range", r, rc->node[r]);
+    if (rc->node[r] < 0 || rc->node[r] >= ctx->nodes.n) KS_FAIL(ctx, KS_EINVAL, "reservation %d: node %d out of range", r, rc->node[r]);
     if (rc->assigned && rc->assigned[r] < 0) KS_FAIL(ctx, KS_EINVAL, "reservation %d: negative assigned count", r);
     if (rc->key_mask[r] >> D) KS_FAIL(ctx, KS_EINVAL, "reservation %d: key_mask has bits beyond KS_RSV_DIMS", r);
   }
@@ -2061,7 +2110,7 @@ static int rsv_install(ks_ctx* ctx, const ks_reservation_cols* rc, int32_t nr, c
   }
   // DeviceShare reservations (deviceshare/reservation.go): a reservation holding devices on a NUMA-policy node is
   // refused (the topology hints would run tryAllocateFromReservation per NUMA mask)
-  std::vector<uint8_t> held((size_t)ctx->n, 0);
+  std::vector<uint8_t> held((size_t)ctx->nodes.n, 0);
   const bool devr = rc && rc->dev_allocatable;
   if (devr) {
     if (check_range64(ctx, rc->dev_allocatable, (int64_t)nr * KS_DEV_WORDS, "reservation dev_allocatable") != KS_OK ||
@@ -2072,7 +2121,7 @@ static int rsv_install(ks_ctx* ctx, const ks_reservation_cols* rc, int32_t nr, c
       bool h = false;
       for (int w = 0; w < KS_DEV_WORDS; ++w) h |= rc->dev_allocatable[(size_t)r * KS_DEV_WORDS + w] != 0;
       if (!h) continue;
-      if ((size_t)rc->node[r] < ctx->h_pol.size() && ctx->h_pol[(size_t)rc->node[r]])
+      if ((size_t)rc->node[r] < ctx->nodes.h_pol.size() && ctx->nodes.h_pol[(size_t)rc->node[r]])
         KS_FAIL(ctx, KS_EUNSUPPORTED, "reservation %d holds devices on node %d, which has a NUMA topology policy", r,
                 rc->node[r]);
       held[(size_t)rc->node[r]] = 1;
@@ -2088,9 +2137,9 @@ static int rsv_install(ks_ctx* ctx, const ks_reservation_cols* rc, int32_t nr, c
   if ((int64_t)(kRsvOrderBase + ndist + 1) * ctx->kc.rsv_F >= ((int64_t)1 << 26))
     KS_FAIL(ctx, KS_EUNSUPPORTED, "too many distinct reservation order labels (%lld) for the key width", (long long)ndist);
   // remove the previous table's base restore
-  if (ctx->rsv_based) {
-    if (rsv_launch_base(ctx, nullptr, ctx->n, -1, 0) != KS_OK) return KS_EHIP;
-    ctx->rsv_based = false;
+  if (ctx->rsv.based) {
+    if (rsv_launch_base(ctx, nullptr, ctx->nodes.n, -1, 0) != KS_OK) return KS_EHIP;
+    ctx->rsv.based = false;
   }
   HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
   std::vector<int32_t> perm(nr);
@@ -2098,7 +2147,7 @@ static int rsv_install(ks_ctx* ctx, const ks_reservation_cols* rc, int32_t nr, c
   std::stable_sort(perm.begin(), perm.end(), [&](int32_t x, int32_t y) { return rc->node[x] < rc->node[y]; });
   const size_t m = (size_t)(nr > 0 ? nr : 1);
   auto al16 = [](size_t x) { return (x + 15) / 16 * 16; };
-  const size_t o_beg = 0, o_cls = al16((size_t)(ctx->npad + 1) * 4), o_meta = o_cls + al16(m * 8),
+  const size_t o_beg = 0, o_cls = al16((size_t)(ctx->nodes.npad + 1) * 4), o_meta = o_cls + al16(m * 8),
                o_ohi = o_meta + al16(m * 4), o_alloc = o_ohi + al16(m * 4), o_allocd = o_alloc + al16(D * m * 8),
                o_asg = o_allocd + al16(D * m * 8), o_rnz = o_asg + al16(m * 4), o_row = o_rnz + al16(2 * m * 8),
                o_ck_allocd = o_row + al16(m * 4), o_ck_asg = o_ck_allocd + al16(D * m * 8),
@@ -2119,14 +2168,14 @@ static int rsv_install(ks_ctx* ctx, const ks_reservation_cols* rc, int32_t nr, c
   int64_t* dald = (int64_t*)(h.data() + o_dald);
   uint32_t* dmask = (uint32_t*)(h.data() + o_dmask);
   for (int32_t i = 0; i < nr; ++i) beg[rc->node[perm[i]] + 1]++;
-  for (int64_t n = 0; n < ctx->npad; ++n) beg[n + 1] += beg[n];
-  ctx->h_rsv_gi.assign((size_t)ncaller, -1);
-  ctx->h_rsv_node.assign((size_t)nr, -1);
+  for (int64_t n = 0; n < ctx->nodes.npad; ++n) beg[n + 1] += beg[n];
+  ctx->rsv.h_gi.assign((size_t)ncaller, -1);
+  ctx->rsv.h_node.assign((size_t)nr, -1);
   for (int32_t i = 0; i < nr; ++i) {
     const int32_t r = perm[i];
     rowid[i] = crow(r);
-    ctx->h_rsv_gi[(size_t)crow(r)] = i;
-    ctx->h_rsv_node[(size_t)i] = rc->node[r];
+    ctx->rsv.h_gi[(size_t)crow(r)] = i;
+    ctx->rsv.h_node[(size_t)i] = rc->node[r];
     cls[i] = rc->owner_classes[r];
     const uint32_t flags = rc->flags ? rc->flags[r] & 0xfu : 0u;
     const uint32_t pol = rc->policy ? std::min<uint32_t>(rc->policy[r], 0xfu) : 0u;
@@ -2161,11 +2210,10 @@ static int rsv_install(ks_ctx* ctx, const ks_reservation_cols* rc, int32_t nr, c
     rnz[m + i] = rc->reserve_nonzero_memory ? rc->reserve_nonzero_memory[r]
                                             : ((keys & 2u) ? alloc[m + i] : kDefaultMemory);
   }
-  dev_free(ctx->rsv_blob);
-  if (dev_alloc(ctx, &ctx->rsv_blob, bytes) != KS_OK) return KS_ENOMEM;
-  HIPCHK(ctx, hipMemcpyAsync(ctx->rsv_blob, h.data(), bytes, hipMemcpyHostToDevice, ctx->stream));
-  char* b = (char*)ctx->rsv_blob;
-  DevRsv& rv = ctx->rv;
+  if (dev_alloc(ctx, ctx->rsv.blob, bytes) != KS_OK) return KS_ENOMEM;
+  HIPCHK(ctx, hipMemcpyAsync(ctx->rsv.blob.get(), h.data(), bytes, hipMemcpyHostToDevice, ctx->stream));
+  char* b = (char*)ctx->rsv.blob.get();
+  DevRsv& rv = ctx->rsv.rv;
   rv.beg = (const int32_t*)(b + o_beg);
   rv.cls = (const uint64_t*)(b + o_cls);
   rv.meta = (const uint32_t*)(b + o_meta);
@@ -2178,27 +2226,23 @@ static int rsv_install(ks_ctx* ctx, const ks_reservation_cols* rc, int32_t nr, c
   rv.dal = (const int64_t*)(b + o_dal);
   rv.dald = (int64_t*)(b + o_dald);
   rv.dmask = (const uint32_t*)(b + o_dmask);
-  ctx->rsv_dald_ckpt = (int64_t*)(b + o_ck_dald);
-  rv.ncls = ctx->d.rsv_cls;
+  rv.ncls = ctx->nodes.d.rsv_cls;
   rv.nr = (int64_t)m;  // row stride of the [dim][row] tables
   rv.w100 = 100 * ctx->cfg.reservation.plugin_weight;
-  ctx->rsv_allocd_ckpt = (int64_t*)(b + o_ck_allocd);
-  ctx->rsv_assigned_ckpt = (int32_t*)(b + o_ck_asg);
-  ctx->rsv_ndist = (int32_t)ndist;
-  ctx->rsv_nrows = ncaller;
-  ctx->rsv_live = nr;
+  ctx->rsv.snap[0] = Snap{rv.allocd, b + o_ck_allocd, D * m * 8};
+  ctx->rsv.snap[1] = Snap{rv.dald, b + o_ck_dald, (size_t)kDevQW * m * 8};
+  ctx->rsv.snap[2] = Snap{rv.assigned, b + o_ck_asg, m * 4};
+  ctx->rsv.ndist = (int32_t)ndist;
+  ctx->rsv.nrows = ncaller;
+  ctx->rsv.live = nr;
   for (int32_t i = 0; i < nr; ++i) perm[i] = crow(perm[i]);
-  ctx->rsv_perm = perm;
-  if (!ctx->drv) {
-    void* p = nullptr;
-    if (dev_alloc(ctx, &p, sizeof(DevRsv)) != KS_OK) return KS_ENOMEM;
-    ctx->drv = (DevRsv*)p;
-  }
-  HIPCHK(ctx, hipMemcpyAsync(ctx->drv, &ctx->rv, sizeof(DevRsv), hipMemcpyHostToDevice, ctx->stream));
+  ctx->rsv.perm = perm;
+  if (!ctx->drv.get() && dev_alloc(ctx, ctx->drv, sizeof(DevRsv)) != KS_OK) return KS_ENOMEM;
+  HIPCHK(ctx, hipMemcpyAsync(ctx->drv.get(), &ctx->rsv.rv, sizeof(DevRsv), hipMemcpyHostToDevice, ctx->stream));
   if (upload_rowcols(ctx) != KS_OK) return KS_ENOMEM;  // row fields RF_RSV_BEG / RF_RSV_END
-  if (rsv_launch_base(ctx, nullptr, ctx->n, +1, 1) != KS_OK) return KS_EHIP;
-  ctx->rsv_based = true;
-  ctx->h_dev_held = held;
+  if (rsv_launch_base(ctx, nullptr, ctx->nodes.n, +1, 1) != KS_OK) return KS_EHIP;
+  ctx->rsv.based = true;
+  ctx->rsv.h_dev_held = held;
   if (int rc = dev_apply_held(ctx); rc != KS_OK) return rc;
   HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
   return KS_OK;
@@ -2292,31 +2336,26 @@ static int dev_encode(ks_ctx* ctx, const ks_device_cols* dc, int64_t rows, size_
 }
 
 static int dev_install(ks_ctx* ctx, const ks_device_cols* dc) {
-  const size_t np = (size_t)ctx->npad, tw = (size_t)kDevTW * np, uw = (size_t)kDevQW * np;
+  const size_t np = (size_t)ctx->nodes.npad, tw = (size_t)kDevTW * np, uw = (size_t)kDevQW * np;
   const size_t o_flags = 0, o_total = (np * 4 + 15) / 16 * 16, o_used = o_total + tw * 8, o_ck = o_used + uw * 8,
                bytes = o_ck + uw * 8;
   std::vector<char> h(bytes, 0);
   uint32_t* flags = (uint32_t*)(h.data() + o_flags);
   int64_t* total = (int64_t*)(h.data() + o_total);
   int64_t* used = (int64_t*)(h.data() + o_used);
-  ctx->h_dev_ids.assign((size_t)ctx->n, 0);
-  if (int rc = dev_encode(ctx, dc, ctx->n, np, flags, total, used, ctx->h_dev_ids.data()); rc != KS_OK) return rc;
-  dev_free(ctx->dev_blob);
-  if (dev_alloc(ctx, &ctx->dev_blob, bytes) != KS_OK) return KS_ENOMEM;
-  HIPCHK(ctx, hipMemcpyAsync(ctx->dev_blob, h.data(), bytes, hipMemcpyHostToDevice, ctx->stream));
-  char* b = (char*)ctx->dev_blob;
-  ctx->dv.flags = (const uint32_t*)(b + o_flags);
-  ctx->dv.total = (const int64_t*)(b + o_total);
-  ctx->dv.used = (int64_t*)(b + o_used);
-  ctx->dv.npad = (int64_t)np;
-  ctx->dev_used_ckpt = (int64_t*)(b + o_ck);
-  if (!ctx->ddv) {
-    void* p = nullptr;
-    if (dev_alloc(ctx, &p, sizeof(DevDev)) != KS_OK) return KS_ENOMEM;
-    ctx->ddv = (DevDev*)p;
-  }
-  HIPCHK(ctx, hipMemcpyAsync(ctx->ddv, &ctx->dv, sizeof(DevDev), hipMemcpyHostToDevice, ctx->stream));
-  ctx->dev_loaded = dc != nullptr;
+  ctx->dev.h_ids.assign((size_t)ctx->nodes.n, 0);
+  if (int rc = dev_encode(ctx, dc, ctx->nodes.n, np, flags, total, used, ctx->dev.h_ids.data()); rc != KS_OK) return rc;
+  if (dev_alloc(ctx, ctx->dev.blob, bytes) != KS_OK) return KS_ENOMEM;
+  HIPCHK(ctx, hipMemcpyAsync(ctx->dev.blob.get(), h.data(), bytes, hipMemcpyHostToDevice, ctx->stream));
+  char* b = (char*)ctx->dev.blob.get();
+  ctx->dev.dv.flags = (const uint32_t*)(b + o_flags);
+  ctx->dev.dv.total = (const int64_t*)(b + o_total);
+  ctx->dev.dv.used = (int64_t*)(b + o_used);
+  ctx->dev.dv.npad = (int64_t)np;
+  ctx->dev.snap[0] = Snap{ctx->dev.dv.used, b + o_ck, uw * 8};
+  if (!ctx->ddv.get() && dev_alloc(ctx, ctx->ddv, sizeof(DevDev)) != KS_OK) return KS_ENOMEM;
+  HIPCHK(ctx, hipMemcpyAsync(ctx->ddv.get(), &ctx->dev.dv, sizeof(DevDev), hipMemcpyHostToDevice, ctx->stream));
+  ctx->dev.loaded = dc != nullptr;
   HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
   if (int rc = dev_apply_held(ctx); rc != KS_OK) return rc;
   return check_dev_numa(ctx);
@@ -2324,25 +2363,25 @@ static int dev_install(ks_ctx* ctx, const ks_device_cols* dc) {
 
 int ks_load_devices(ks_ctx* ctx, const ks_device_cols* dev, int64_t n) {
   if (!ctx || !dev) return ctx ? (ctx->err = "ks_load_devices: bad args", KS_EINVAL) : KS_EINVAL;
-  if (!ctx->node_blob) KS_FAIL(ctx, KS_ESTATE, "ks_load_devices before ks_load_nodes");
-  if (n != ctx->n) KS_FAIL(ctx, KS_EINVAL, "ks_load_devices: %lld rows for %lld nodes", (long long)n, (long long)ctx->n);
+  if (!ctx->nodes.blob.get()) KS_FAIL(ctx, KS_ESTATE, "ks_load_devices before ks_load_nodes");
+  if (n != ctx->nodes.n) KS_FAIL(ctx, KS_EINVAL, "ks_load_devices: %lld rows for %lld nodes", (long long)n, (long long)ctx->nodes.n);
   if (!ctx->cfg.deviceshare.enable) KS_FAIL(ctx, KS_ESTATE, "ks_load_devices: the DeviceShare plugin is not enabled");
   HIPCHK(ctx, hipSetDevice(ctx->device));
-  ctx->h_dev_assumed.clear();  // a full reload carries its own usage
+  ctx->dev.h_assumed.clear();  // a full reload carries its own usage
   return dev_install(ctx, dev);
 }
 
 static int read_dev_used(ks_ctx* ctx, std::vector<int64_t>& u) {
-  u.resize((size_t)kDevQW * (size_t)ctx->npad);
-  HIPCHK(ctx, hipMemcpyAsync(u.data(), ctx->dv.used, u.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
+  u.resize((size_t)kDevQW * (size_t)ctx->nodes.npad);
+  HIPCHK(ctx, hipMemcpyAsync(u.data(), ctx->dev.dv.used, u.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
   HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
   return KS_OK;
 }
 
 int ks_read_devices(ks_ctx* ctx, int64_t* used_core, int64_t* used_memory, int64_t* used_ratio) {
   if (!ctx) return KS_EINVAL;
-  if (!ctx->dev_blob) return KS_OK;
-  const size_t np = (size_t)ctx->npad, n = (size_t)ctx->n;
+  if (!ctx->dev.blob.get()) return KS_OK;
+  const size_t np = (size_t)ctx->nodes.npad, n = (size_t)ctx->nodes.n;
   std::vector<int64_t> u;
   if (read_dev_used(ctx, u) != KS_OK) return KS_EHIP;
   int64_t* outs[3] = {used_core, used_memory, used_ratio};
@@ -2354,8 +2393,8 @@ int ks_read_devices(ks_ctx* ctx, int64_t* used_core, int64_t* used_memory, int64
 
 int ks_read_devices_rdma(ks_ctx* ctx, int64_t* used_rdma) {
   if (!ctx || !used_rdma) return KS_EINVAL;
-  if (!ctx->dev_blob) return KS_OK;
-  const size_t np = (size_t)ctx->npad, n = (size_t)ctx->n;
+  if (!ctx->dev.blob.get()) return KS_OK;
+  const size_t np = (size_t)ctx->nodes.npad, n = (size_t)ctx->nodes.n;
   std::vector<int64_t> u;
   if (read_dev_used(ctx, u) != KS_OK) return KS_EHIP;
   for (int j = 0; j < kRdma; ++j) memcpy(used_rdma + (size_t)j * n, u.data() + ((size_t)kDevRdmaW + j) * np, n * 8);
@@ -2460,10 +2499,10 @@ static int cpu_encode_row(ks_ctx* ctx, const ks_cpu_state_cols* st, int64_t i, i
 int ks_load_cpu_state(ks_ctx* ctx, const ks_cpu_topology* topos, int32_t ntopo, const ks_cpu_state_cols* st) {
   if (!ctx || ntopo < 0 || (ntopo > 0 && !topos) || !st || !st->topology || !st->allocated)
     return ctx ? (ctx->err = "ks_load_cpu_state: bad args", KS_EINVAL) : KS_EINVAL;
-  if (!ctx->node_blob) KS_FAIL(ctx, KS_ESTATE, "ks_load_cpu_state before ks_load_nodes");
+  if (!ctx->nodes.blob.get()) KS_FAIL(ctx, KS_ESTATE, "ks_load_cpu_state before ks_load_nodes");
   if (!ctx->cfg.numa.enable) KS_FAIL(ctx, KS_ESTATE, "ks_load_cpu_state: the NodeNUMAResource plugin is not enabled");
   HIPCHK(ctx, hipSetDevice(ctx->device));
-  const int64_t n = ctx->n, np = ctx->npad;
+  const int64_t n = ctx->nodes.n, np = ctx->nodes.npad;
   std::vector<CpuTopo> tt((size_t)std::max(ntopo, 1));
   std::vector<int32_t> cpc;
   std::vector<int8_t> dense((size_t)std::max(ntopo, 1), 1);
@@ -2479,12 +2518,11 @@ int ks_load_cpu_state(ks_ctx* ctx, const ks_cpu_topology* topos, int32_t ntopo, 
   for (int64_t i = 0; i < n; ++i)
     if (int rc = cpu_encode_row(ctx, st, i, i, ntopo, tt, tid[i], al[i], xp[i], xn[i], rs[i], freec[i], ncpu[i]); rc != KS_OK)
       return rc;
-  dev_free(ctx->cpu_blob);
-  ctx->cpu_loaded = false;
+  ctx->cpus.loaded = false;
   const size_t tb = align16(tt.size() * sizeof(CpuTopo)), ib = align16((size_t)np * 4), sb = (size_t)np * sizeof(CpuSet);
-  if (dev_alloc(ctx, &ctx->cpu_blob, tb + ib + sb * 7) != KS_OK) return KS_ENOMEM;
-  char* b = (char*)ctx->cpu_blob;
-  DevCpu& c = ctx->cpu;
+  if (dev_alloc(ctx, ctx->cpus.blob, tb + ib + sb * 7) != KS_OK) return KS_ENOMEM;
+  char* b = (char*)ctx->cpus.blob.get();
+  DevCpu& c = ctx->cpus.cpu;
   c.topo = (const CpuTopo*)b;
   HIPCHK(ctx, hipMemcpyAsync(b, tt.data(), tt.size() * sizeof(CpuTopo), hipMemcpyHostToDevice, ctx->stream));
   b += tb;
@@ -2502,21 +2540,21 @@ int ks_load_cpu_state(ks_ctx* ctx, const ks_cpu_topology* topos, int32_t ntopo, 
   c.excl_pcpu = sets[1];
   c.excl_numa = sets[2];
   c.reserved = sets[3];
-  ctx->cpu_ckpt = (CpuSet*)b;  // 3 x [npad]
-  HIPCHK(ctx, hipMemcpyAsync(ctx->cpu_ckpt, c.allocated, sb * 3, hipMemcpyDeviceToDevice, ctx->stream));
+  ctx->cpus.snap[0] = Snap{c.allocated, b, sb * 3};  // allocated, excl_pcpu, excl_numa: 3 x [npad]
+  if (snap_copy(ctx, ctx->cpus.snap[0], false) != KS_OK) return KS_EHIP;
   c.npad = np;
   c.ntopo = ntopo;
-  HIPCHK(ctx, hipMemcpyAsync(ctx->d.cpu_free, freec.data(), (size_t)np * 4, hipMemcpyHostToDevice, ctx->stream));
-  HIPCHK(ctx, hipMemcpyAsync(ctx->d.numa_cpus, ncpu.data(), (size_t)np * 4, hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(ctx, hipMemcpyAsync(ctx->nodes.d.cpu_free, freec.data(), (size_t)np * 4, hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(ctx, hipMemcpyAsync(ctx->nodes.d.numa_cpus, ncpu.data(), (size_t)np * 4, hipMemcpyHostToDevice, ctx->stream));
   if (upload_prep_nodes(ctx) != KS_OK) return KS_EHIP;  // re-derive the cpuset millicores and offsets
   HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-  ctx->cpu_cpc = cpc;
-  ctx->cpu_loaded = true;
-  ctx->h_topos = tt;
-  ctx->h_topo_dense = dense;
-  ctx->h_cpu_nn.assign((size_t)n, 0);
+  ctx->cpus.cpc = cpc;
+  ctx->cpus.loaded = true;
+  ctx->cpus.h_topos = tt;
+  ctx->cpus.h_topo_dense = dense;
+  ctx->cpus.h_nn.assign((size_t)n, 0);
   for (int64_t i = 0; i < n; ++i)
-    if (const int32_t ti = tid[(size_t)i]; ti >= 0) ctx->h_cpu_nn[(size_t)i] = dense[(size_t)ti] ? (int8_t)tt[(size_t)ti].nnodes : (int8_t)-1;
+    if (const int32_t ti = tid[(size_t)i]; ti >= 0) ctx->cpus.h_nn[(size_t)i] = dense[(size_t)ti] ? (int8_t)tt[(size_t)ti].nnodes : (int8_t)-1;
   if (int rc = numa_refresh_free(ctx); rc != KS_OK) return rc;
   if (int rc = cores_refresh(ctx); rc != KS_OK) return rc;
   HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
@@ -2525,10 +2563,10 @@ int ks_load_cpu_state(ks_ctx* ctx, const ks_cpu_topology* topos, int32_t ntopo, 
 
 int ks_read_cpu_state(ks_ctx* ctx, uint64_t* allocated, uint64_t* excl_pcpu, uint64_t* excl_numa) {
   if (!ctx) return KS_EINVAL;
-  if (!ctx->cpu_loaded) return KS_OK;
-  const size_t n = (size_t)ctx->n;
+  if (!ctx->cpus.loaded) return KS_OK;
+  const size_t n = (size_t)ctx->nodes.n;
   uint64_t* outs[3] = {allocated, excl_pcpu, excl_numa};
-  const CpuSet* srcs[3] = {ctx->cpu.allocated, ctx->cpu.excl_pcpu, ctx->cpu.excl_numa};
+  const CpuSet* srcs[3] = {ctx->cpus.cpu.allocated, ctx->cpus.cpu.excl_pcpu, ctx->cpus.cpu.excl_numa};
   for (int q = 0; q < 3; ++q)
     if (outs[q] && n) HIPCHK(ctx, hipMemcpyAsync(outs[q], srcs[q], n * sizeof(CpuSet), hipMemcpyDeviceToHost, ctx->stream));
   HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
@@ -2537,8 +2575,8 @@ int ks_read_cpu_state(ks_ctx* ctx, uint64_t* allocated, uint64_t* excl_pcpu, uin
 
 int ks_fetch_cpusets(ks_ctx* ctx, uint64_t* out, int32_t p) {
   if (!ctx || (p > 0 && !out) || p < 0) return ctx ? (ctx->err = "ks_fetch_cpusets: bad args", KS_EINVAL) : KS_EINVAL;
-  if (p > ctx->np) KS_FAIL(ctx, KS_EINVAL, "ks_fetch_cpusets: %d pods requested, %d scheduled", p, ctx->np);
-  if (p > 0 && ctx->cpusets_clobbered) KS_FAIL(ctx, KS_ESTATE, "ks_fetch_cpusets: a ks_assume since the last schedule overwrote them");
+  if (p > ctx->staged.np) KS_FAIL(ctx, KS_EINVAL, "ks_fetch_cpusets: %d pods requested, %d scheduled", p, ctx->staged.np);
+  if (p > 0 && ctx->staged.cpusets_clobbered) KS_FAIL(ctx, KS_ESTATE, "ks_fetch_cpusets: a ks_assume since the last schedule overwrote them");
   if (p == 0) return KS_OK;
   if (!ctx->cpuset_out || ctx->cpuset_cap < p) {
     memset(out, 0, (size_t)p * sizeof(CpuSet));
@@ -2551,40 +2589,38 @@ int ks_fetch_cpusets(ks_ctx* ctx, uint64_t* out, int32_t p) {
 
 // NUMA nodes' available CPUs from the CPU state (numa_free_kernel); zero without a loaded CPU state
 static int numa_refresh_free(ks_ctx* ctx) {
-  if (!ctx->numa_blob) return KS_OK;
-  const size_t np = (size_t)ctx->npad;
-  if (!ctx->cpu_loaded) {
-    HIPCHK(ctx, hipMemsetAsync(ctx->nv.free, 0, (size_t)ctx->numa_w * np * 4, ctx->stream));
+  if (!ctx->numa.blob.get()) return KS_OK;
+  const size_t np = (size_t)ctx->nodes.npad;
+  if (!ctx->cpus.loaded) {
+    HIPCHK(ctx, hipMemsetAsync(ctx->numa.nv.free, 0, (size_t)ctx->numa.w * np * 4, ctx->stream));
     return KS_OK;
   }
   // the per-NUMA cpuset takes index the topology's NUMA nodes by NUMA id, and a cpu-bind pod admitted with a nil
   // affinity (single NUMA node) takes from NUMA node 0: the CPU topology's NUMA ids are 0..m-1 with m <= the count
-  for (int64_t i = 0; i < ctx->n && i < (int64_t)ctx->h_numa_k.size() && i < (int64_t)ctx->h_cpu_nn.size(); ++i) {
-    const int k = ctx->h_numa_k[(size_t)i], m = ctx->h_cpu_nn[(size_t)i];
+  for (int64_t i = 0; i < ctx->nodes.n && i < (int64_t)ctx->numa.h_k.size() && i < (int64_t)ctx->cpus.h_nn.size(); ++i) {
+    const int k = ctx->numa.h_k[(size_t)i], m = ctx->cpus.h_nn[(size_t)i];
     if (k > 0 && m != 0 && (m < 0 || m > k))
       KS_FAIL(ctx, KS_EUNSUPPORTED, "node %lld: NUMA-policy node whose CPU topology NUMA ids are not 0..m-1 with m <= %d",
               (long long)i, k);
   }
-  if (ctx->n > 0) {
-    const dim3 grid((unsigned)((ctx->n + 255) / 256));
-    if (ctx->numa_w == kNumaWide) hipLaunchKernelGGL(numa_free_kernel<kNumaWide>, grid, dim3(256), 0, ctx->stream, ctx->cpu, ctx->nv, ctx->n);
-    else hipLaunchKernelGGL(numa_free_kernel<kNumaDev>, grid, dim3(256), 0, ctx->stream, ctx->cpu, ctx->nv, ctx->n);
+  if (ctx->nodes.n > 0) {
+    const dim3 grid((unsigned)((ctx->nodes.n + 255) / 256));
+    if (ctx->numa.w == kNumaWide) hipLaunchKernelGGL(numa_free_kernel<kNumaWide>, grid, dim3(256), 0, ctx->stream, ctx->cpus.cpu, ctx->numa.nv, ctx->nodes.n);
+    else hipLaunchKernelGGL(numa_free_kernel<kNumaDev>, grid, dim3(256), 0, ctx->stream, ctx->cpus.cpu, ctx->numa.nv, ctx->nodes.n);
   }
   HIPCHK(ctx, hipGetLastError());
   // a load re-bases the checkpoint (as the CPU state's own checkpoint is re-based by ks_load_cpu_state)
-  char* ck_free = ctx->numa_ckpt + ((char*)ctx->nv.free - (char*)ctx->nv.used);
-  HIPCHK(ctx, hipMemcpyAsync(ck_free, ctx->nv.free, (size_t)ctx->numa_w * np * 4, hipMemcpyDeviceToDevice, ctx->stream));
-  return KS_OK;
+  return snap_copy(ctx, ctx->numa.free_snap, false);
 }
 
 // DeviceShare as a hint provider on NUMA-policy nodes: its hint masks range over the device topology's NUMA nodes,
 // which must be NUMA nodes of the node (ids < its NUMA count), at most kDevHintIds of them, on nodes with at most
 // kDevHintIds NUMA nodes (this bounds the merge's cartesian product, ks_numa.h).
 static int check_dev_numa(ks_ctx* ctx) {
-  if (!ctx->cfg.deviceshare.enable || ctx->h_numa_k.empty() || ctx->h_dev_ids.empty()) return KS_OK;
-  for (int64_t i = 0; i < ctx->n; ++i) {
-    const int k = ctx->h_numa_k[(size_t)i];
-    const uint32_t ids = ctx->h_dev_ids[(size_t)i];
+  if (!ctx->cfg.deviceshare.enable || ctx->numa.h_k.empty() || ctx->dev.h_ids.empty()) return KS_OK;
+  for (int64_t i = 0; i < ctx->nodes.n; ++i) {
+    const int k = ctx->numa.h_k[(size_t)i];
+    const uint32_t ids = ctx->dev.h_ids[(size_t)i];
     if (k == 0 || ids == 0) continue;
     if (k > kDevHintIds || __builtin_popcount(ids) > kDevHintIds || (ids >> k) != 0)
       KS_FAIL(ctx, KS_EUNSUPPORTED,
@@ -2597,9 +2633,6 @@ static int check_dev_numa(ks_ctx* ctx) {
 // NUMA node resources of the policy nodes; nc == nullptr installs an empty table (every policy node
 // then reports "missing NUMA resources", as the reference does without a NodeResourceTopology).
 // Layout: count | total | mutable {used, off, cs, free, present} | checkpoint copy of the mutable block.
-static size_t numa_mut_bytes(size_t np, int K) {
-  return 2 * K * np * 8 + K * np * 8 + 2 * K * np * 4 + align16(np * 4);
-}
 
 // One node's NUMA-node table words (ks_numa.h layout): row r of nc describes node `node` (numa_flags f, cpu
 // amplification ratio).  Only NUMA-policy nodes carry resources; the policy-None path never reads them.
@@ -2645,17 +2678,17 @@ static int numa_encode(ks_ctx* ctx, const ks_numa_node_cols* nc, int64_t r, int6
 }
 
 static int numa_install(ks_ctx* ctx, const ks_numa_node_cols* nc, const uint32_t* flags_h, const double* ratio_h) {
-  const size_t np = (size_t)ctx->npad;
+  const size_t np = (size_t)ctx->nodes.npad;
   // the width: 8 once a policy node has more than 4 NUMA nodes (the 4-wide kernels are the faster ones)
   int K = kNumaDev;
-  for (int64_t i = 0; nc && i < ctx->n; ++i)
+  for (int64_t i = 0; nc && i < ctx->nodes.n; ++i)
     if (((flags_h[i] >> KS_NUMA_POLICY_SHIFT) & 3u) != 0 && nc->count[i] > kNumaDev && nc->count[i] <= KS_MAX_NUMA) K = kNumaWide;
-  if (K == kNumaWide && ctx->kc.rsv && ctx->kc.dev && ctx->dev_held_any)  // (FEAT 31 is built at width 4 only)
+  if (K == kNumaWide && ctx->kc.rsv && ctx->kc.dev && ctx->rsv.dev_held_any)  // (FEAT 31 is built at width 4 only)
     KS_FAIL(ctx, KS_EUNSUPPORTED,
             "reservations holding devices together with a NUMA-policy node with more than %d NUMA nodes", kNumaDev);
   const size_t o_cnt = 0, o_tot = align16(np * 4), o_used = o_tot + 2 * K * np * 8, o_off = o_used + 2 * K * np * 8,
                o_cs = o_off + K * np * 8, o_free = o_cs + K * np * 4, o_pres = o_free + K * np * 4,
-               o_ck = o_pres + align16(np * 4), bytes = o_ck + numa_mut_bytes(np, K);
+               o_ck = o_pres + align16(np * 4), bytes = o_ck + (o_ck - o_used);  // (the mutable block twice)
   std::vector<char> h(bytes, 0);
   int32_t* cnt = (int32_t*)(h.data() + o_cnt);
   int64_t* tot = (int64_t*)(h.data() + o_tot);
@@ -2663,12 +2696,12 @@ static int numa_install(ks_ctx* ctx, const ks_numa_node_cols* nc, const uint32_t
   int64_t* off = (int64_t*)(h.data() + o_off);
   int32_t* csv = (int32_t*)(h.data() + o_cs);
   uint32_t* pres = (uint32_t*)(h.data() + o_pres);
-  ctx->h_numa_k.assign((size_t)ctx->n, 0);
-  for (int64_t i = 0; nc && i < ctx->n; ++i) {
+  ctx->numa.h_k.assign((size_t)ctx->nodes.n, 0);
+  for (int64_t i = 0; nc && i < ctx->nodes.n; ++i) {
     NumaRow w;
     if (int rc = numa_encode(ctx, nc, i, i, flags_h[i], ratio_h ? ratio_h[i] : 0.0, K, w); rc != KS_OK) return rc;
     cnt[i] = w.cnt;
-    ctx->h_numa_k[(size_t)i] = (int8_t)w.cnt;
+    ctx->numa.h_k[(size_t)i] = (int8_t)w.cnt;
     pres[i] = w.pres;
     for (int k = 0; k < K; ++k) {
       for (int q = 0; q < 2; ++q) {
@@ -2679,12 +2712,11 @@ static int numa_install(ks_ctx* ctx, const ks_numa_node_cols* nc, const uint32_t
       csv[(size_t)k * np + i] = w.cs[k];
     }
   }
-  dev_free(ctx->numa_blob);
-  if (dev_alloc(ctx, &ctx->numa_blob, bytes) != KS_OK) return KS_ENOMEM;
-  ctx->numa_w = K;
-  char* b = (char*)ctx->numa_blob;
+  if (dev_alloc(ctx, ctx->numa.blob, bytes) != KS_OK) return KS_ENOMEM;
+  ctx->numa.w = K;
+  char* b = (char*)ctx->numa.blob.get();
   HIPCHK(ctx, hipMemcpyAsync(b, h.data(), bytes, hipMemcpyHostToDevice, ctx->stream));
-  DevNuma& v = ctx->nv;
+  DevNuma& v = ctx->numa.nv;
   v.count = (const int32_t*)(b + o_cnt);
   v.total = (const int64_t*)(b + o_tot);
   v.used = (int64_t*)(b + o_used);
@@ -2692,27 +2724,28 @@ static int numa_install(ks_ctx* ctx, const ks_numa_node_cols* nc, const uint32_t
   v.cs = (int32_t*)(b + o_cs);
   v.free = (int32_t*)(b + o_free);
   v.present = (uint32_t*)(b + o_pres);
-  v.flags = ctx->d.numa_flags;
-  v.npad = ctx->npad;
-  ctx->numa_ckpt = b + o_ck;
-  HIPCHK(ctx, hipMemcpyAsync(ctx->dnv, &v, sizeof(DevNuma), hipMemcpyHostToDevice, ctx->stream));
+  v.flags = ctx->nodes.d.numa_flags;
+  v.npad = ctx->nodes.npad;
+  ctx->numa.snap[0] = Snap{v.used, b + o_ck, o_ck - o_used};
+  ctx->numa.free_snap = Snap{v.free, b + o_ck + (o_free - o_used), K * np * 4};
+  HIPCHK(ctx, hipMemcpyAsync(ctx->dnv.get(), &v, sizeof(DevNuma), hipMemcpyHostToDevice, ctx->stream));
   if (int rc = numa_refresh_free(ctx); rc != KS_OK) return rc;
-  HIPCHK(ctx, hipMemcpyAsync(ctx->numa_ckpt, v.used, numa_mut_bytes(np, ctx->numa_w), hipMemcpyDeviceToDevice, ctx->stream));
+  if (snap_copy(ctx, ctx->numa.snap[0], false) != KS_OK) return KS_EHIP;
   HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
   return check_dev_numa(ctx);
 }
 
 int ks_load_numa_nodes(ks_ctx* ctx, const ks_numa_node_cols* nc) {
   if (!ctx || !nc || !nc->count) return ctx ? (ctx->err = "ks_load_numa_nodes: bad args", KS_EINVAL) : KS_EINVAL;
-  if (!ctx->node_blob) KS_FAIL(ctx, KS_ESTATE, "ks_load_numa_nodes before ks_load_nodes");
+  if (!ctx->nodes.blob.get()) KS_FAIL(ctx, KS_ESTATE, "ks_load_numa_nodes before ks_load_nodes");
   if (!ctx->cfg.numa.enable) KS_FAIL(ctx, KS_ESTATE, "ks_load_numa_nodes: the NodeNUMAResource plugin is not enabled");
   HIPCHK(ctx, hipSetDevice(ctx->device));
-  const size_t n = (size_t)ctx->n;
+  const size_t n = (size_t)ctx->nodes.n;
   std::vector<uint32_t> flags(n ? n : 1);
   std::vector<double> ratio(n ? n : 1);
   if (n) {
-    HIPCHK(ctx, hipMemcpyAsync(flags.data(), ctx->d.numa_flags, n * 4, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(ratio.data(), ctx->d.numa_ratio, n * 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(flags.data(), ctx->nodes.d.numa_flags, n * 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(ratio.data(), ctx->nodes.d.numa_ratio, n * 8, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
   }
   return numa_install(ctx, nc, flags.data(), ratio.data());
@@ -2728,18 +2761,18 @@ static int check_idx(ks_ctx* ctx, const int32_t* idx, int64_t m, int64_t lim, co
 int ks_update_numa_nodes(ks_ctx* ctx, const int32_t* idx, const ks_numa_node_cols* rows, int64_t m) {
   if (!ctx || !rows || m < 0 || (m > 0 && (!idx || !rows->count)))
     return ctx ? (ctx->err = "ks_update_numa_nodes: bad args", KS_EINVAL) : KS_EINVAL;
-  if (!ctx->numa_blob) KS_FAIL(ctx, KS_ESTATE, "ks_update_numa_nodes: no NUMA-node table (no node has a NUMA policy)");
+  if (!ctx->numa.blob.get()) KS_FAIL(ctx, KS_ESTATE, "ks_update_numa_nodes: no NUMA-node table (no node has a NUMA policy)");
   std::vector<int32_t> ix;
-  if (int rc = check_idx(ctx, idx, m, ctx->n, "ks_update_numa_nodes", ix); rc != KS_OK) return rc;
+  if (int rc = check_idx(ctx, idx, m, ctx->nodes.n, "ks_update_numa_nodes", ix); rc != KS_OK) return rc;
   if (m == 0) return KS_OK;
   HIPCHK(ctx, hipSetDevice(ctx->device));
-  const size_t n = (size_t)ctx->n;
+  const size_t n = (size_t)ctx->nodes.n;
   std::vector<uint32_t> flags(n);
   std::vector<double> ratio(n);
-  HIPCHK(ctx, hipMemcpyAsync(flags.data(), ctx->d.numa_flags, n * 4, hipMemcpyDeviceToHost, ctx->stream));
-  HIPCHK(ctx, hipMemcpyAsync(ratio.data(), ctx->d.numa_ratio, n * 8, hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(ctx, hipMemcpyAsync(flags.data(), ctx->nodes.d.numa_flags, n * 4, hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(ctx, hipMemcpyAsync(ratio.data(), ctx->nodes.d.numa_ratio, n * 8, hipMemcpyDeviceToHost, ctx->stream));
   HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-  const int K = ctx->numa_w;
+  const int K = ctx->numa.w;
   std::vector<int32_t> cnt((size_t)m), cs((size_t)m * K);
   std::vector<uint32_t> pres((size_t)m);
   std::vector<int64_t> tot((size_t)m * 2 * K), used((size_t)m * 2 * K), off((size_t)m * K);
@@ -2759,8 +2792,8 @@ int ks_update_numa_nodes(ks_ctx* ctx, const int32_t* idx, const ks_numa_node_col
       cs[(size_t)q * m + i] = w.cs[q];
     }
   }
-  const int64_t np = ctx->npad;
-  DevNuma& v = ctx->nv;
+  const int64_t np = ctx->nodes.npad;
+  DevNuma& v = ctx->numa.nv;
   if (scatter_words(ctx, (void*)v.count, 4, 1, np, 1, ix, cnt.data()) != KS_OK ||
       scatter_words(ctx, (void*)v.present, 4, 1, np, 1, ix, pres.data()) != KS_OK ||
       scatter_words(ctx, (void*)v.total, 8, 1, np, 2 * K, ix, tot.data()) != KS_OK ||
@@ -2768,7 +2801,7 @@ int ks_update_numa_nodes(ks_ctx* ctx, const int32_t* idx, const ks_numa_node_col
       scatter_words(ctx, (void*)v.off, 8, 1, np, K, ix, off.data()) != KS_OK ||
       scatter_words(ctx, (void*)v.cs, 4, 1, np, K, ix, cs.data()) != KS_OK)
     return KS_EHIP;
-  for (int64_t i = 0; i < m; ++i) ctx->h_numa_k[(size_t)ix[(size_t)i]] = (int8_t)cnt[(size_t)i];
+  for (int64_t i = 0; i < m; ++i) ctx->numa.h_k[(size_t)ix[(size_t)i]] = (int8_t)cnt[(size_t)i];
   if (int rc = numa_refresh_free(ctx); rc != KS_OK) return rc;
   HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
   return check_dev_numa(ctx);
@@ -2776,12 +2809,12 @@ int ks_update_numa_nodes(ks_ctx* ctx, const int32_t* idx, const ks_numa_node_col
 
 int ks_read_numa_nodes(ks_ctx* ctx, int64_t* used_cpu, int64_t* used_memory) {
   if (!ctx) return KS_EINVAL;
-  const size_t n = (size_t)ctx->n, np = (size_t)ctx->npad;
-  const int W = ctx->numa_w;
+  const size_t n = (size_t)ctx->nodes.n, np = (size_t)ctx->nodes.npad;
+  const int W = ctx->numa.w;
   std::vector<int64_t> u((size_t)2 * W * (np ? np : 1), 0);
   std::vector<uint32_t> pr(np ? np : 1, 0);
-  if (ctx->numa_blob && n) {
-    HIPCHK(ctx, hipMemcpyAsync(u.data(), ctx->nv.used, u.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
+  if (ctx->numa.blob.get() && n) {
+    HIPCHK(ctx, hipMemcpyAsync(u.data(), ctx->numa.nv.used, u.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
   }
   int64_t* outs[2] = {used_cpu, used_memory};
@@ -2796,7 +2829,7 @@ int ks_read_numa_nodes(ks_ctx* ctx, int64_t* used_cpu, int64_t* used_memory) {
 // rows of rc appended to the host mirror (NULL columns as rsv_install reads them; the reserve pod's NonZeroRequested
 // resolved the same way)
 static void rsv_mirror_append(ks_ctx* ctx, const ks_reservation_cols* rc, int32_t nr) {
-  auto& M = ctx->rmir;
+  auto& M = ctx->rsv.rmir;
   for (int32_t r = 0; r < nr; ++r) {
     M.node.push_back(rc->node[r]);
     M.cls.push_back(rc->owner_classes[r]);
@@ -2824,11 +2857,11 @@ static void rsv_mirror_append(ks_ctx* ctx, const ks_reservation_cols* rc, int32_
 
 int ks_load_reservations(ks_ctx* ctx, const ks_reservation_cols* rsv, int32_t r) {
   if (!ctx || r < 0 || (r > 0 && !rsv)) return ctx ? (ctx->err = "ks_load_reservations: bad args", KS_EINVAL) : KS_EINVAL;
-  if (!ctx->node_blob) KS_FAIL(ctx, KS_ESTATE, "ks_load_reservations before ks_load_nodes");
+  if (!ctx->nodes.blob.get()) KS_FAIL(ctx, KS_ESTATE, "ks_load_reservations before ks_load_nodes");
   if (!ctx->cfg.reservation.enable) KS_FAIL(ctx, KS_ESTATE, "ks_load_reservations: the Reservation plugin is not enabled");
   HIPCHK(ctx, hipSetDevice(ctx->device));
   if (int rc = rsv_install(ctx, rsv, r); rc != KS_OK) return rc;
-  ctx->rmir = ks_ctx::RsvMirror{};
+  ctx->rsv.rmir = RsvMirror{};
   rsv_mirror_append(ctx, rsv, r);
   return KS_OK;
 }
@@ -2839,20 +2872,20 @@ int ks_load_reservations(ks_ctx* ctx, const ks_reservation_cols* rsv, int32_t r)
 // columns' base restore follows, rsv_install).  Caller row numbers stay stable: added rows get the next numbers,
 // deleted rows leave gaps.
 static int rsv_reinstall(ks_ctx* ctx) {
-  auto& M = ctx->rmir;
+  auto& M = ctx->rsv.rmir;
   const int32_t total = (int32_t)M.node.size();
-  if (ctx->rsv_blob && ctx->rsv_live > 0) {
+  if (ctx->rsv.blob.get() && ctx->rsv.live > 0) {
     // the device's Allocated / assigned (commits since the last install) into the mirror
-    const size_t m = (size_t)ctx->rv.nr;
+    const size_t m = (size_t)ctx->rsv.rv.nr;
     std::vector<int64_t> ad(kRsvDims * m);
     std::vector<int32_t> as(m);
-    HIPCHK(ctx, hipMemcpyAsync(ad.data(), ctx->rv.allocd, ad.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(as.data(), ctx->rv.assigned, m * 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(ad.data(), ctx->rsv.rv.allocd, ad.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(as.data(), ctx->rsv.rv.assigned, m * 4, hipMemcpyDeviceToHost, ctx->stream));
     std::vector<int64_t> dd((size_t)kDevQW * m);
-    HIPCHK(ctx, hipMemcpyAsync(dd.data(), ctx->rv.dald, dd.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(dd.data(), ctx->rsv.rv.dald, dd.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
     HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    for (int32_t i = 0; i < ctx->rsv_live; ++i) {
-      const int32_t r = ctx->rsv_perm[(size_t)i];
+    for (int32_t i = 0; i < ctx->rsv.live; ++i) {
+      const int32_t r = ctx->rsv.perm[(size_t)i];
       for (int d = 0; d < kRsvDims; ++d) M.allocd[d][(size_t)r] = ad[(size_t)d * m + i];
       M.assigned[(size_t)r] = as[(size_t)i];
       for (int w = 0; w < kDevQW; ++w) M.dald[(size_t)r * KS_DEV_WORDS + w] = dd[(size_t)w * m + i];
@@ -2910,16 +2943,16 @@ static int rsv_reinstall(ks_ctx* ctx) {
 
 int ks_add_reservations(ks_ctx* ctx, const ks_reservation_cols* rsv, int32_t r, int32_t* first_row) {
   if (!ctx || r < 0 || (r > 0 && !rsv)) return ctx ? (ctx->err = "ks_add_reservations: bad args", KS_EINVAL) : KS_EINVAL;
-  if (!ctx->node_blob) KS_FAIL(ctx, KS_ESTATE, "ks_add_reservations before ks_load_nodes");
+  if (!ctx->nodes.blob.get()) KS_FAIL(ctx, KS_ESTATE, "ks_add_reservations before ks_load_nodes");
   if (!ctx->cfg.reservation.enable) KS_FAIL(ctx, KS_ESTATE, "ks_add_reservations: the Reservation plugin is not enabled");
   HIPCHK(ctx, hipSetDevice(ctx->device));
-  const int32_t first = (int32_t)ctx->rmir.node.size();
+  const int32_t first = (int32_t)ctx->rsv.rmir.node.size();
   if (first_row) *first_row = first;
   if (r == 0) return KS_OK;
-  const ks_ctx::RsvMirror saved = ctx->rmir;
+  const RsvMirror saved = ctx->rsv.rmir;
   rsv_mirror_append(ctx, rsv, r);
   if (int rc = rsv_reinstall(ctx); rc != KS_OK) {
-    ctx->rmir = saved;  // the previous table stays installed when validation refused the new rows
+    ctx->rsv.rmir = saved;  // the previous table stays installed when validation refused the new rows
     return rc;
   }
   return KS_OK;
@@ -2928,7 +2961,7 @@ int ks_add_reservations(ks_ctx* ctx, const ks_reservation_cols* rsv, int32_t r, 
 int ks_delete_reservations(ks_ctx* ctx, const int32_t* rows, int32_t m) {
   if (!ctx || m < 0 || (m > 0 && !rows)) return ctx ? (ctx->err = "ks_delete_reservations: bad args", KS_EINVAL) : KS_EINVAL;
   if (!ctx->cfg.reservation.enable) KS_FAIL(ctx, KS_ESTATE, "ks_delete_reservations: the Reservation plugin is not enabled");
-  auto& M = ctx->rmir;
+  auto& M = ctx->rsv.rmir;
   for (int32_t i = 0; i < m; ++i)
     if (rows[i] < 0 || (size_t)rows[i] >= M.live.size() || !M.live[(size_t)rows[i]])
       KS_FAIL(ctx, KS_EINVAL, "ks_delete_reservations: row %d is not a loaded reservation", rows[i]);
@@ -2940,16 +2973,16 @@ int ks_delete_reservations(ks_ctx* ctx, const int32_t* rows, int32_t m) {
 
 int ks_read_reservations(ks_ctx* ctx, int64_t* allocated, int32_t* assigned) {
   if (!ctx) return KS_EINVAL;
-  const int32_t nr = ctx->rsv_live;
-  if (nr == 0 || !ctx->rsv_blob) return KS_OK;
-  const size_t m = (size_t)ctx->rv.nr;
+  const int32_t nr = ctx->rsv.live;
+  if (nr == 0 || !ctx->rsv.blob.get()) return KS_OK;
+  const size_t m = (size_t)ctx->rsv.rv.nr;
   std::vector<int64_t> ad(kRsvDims * m);
   std::vector<int32_t> as(m);
-  HIPCHK(ctx, hipMemcpyAsync(ad.data(), ctx->rv.allocd, ad.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
-  HIPCHK(ctx, hipMemcpyAsync(as.data(), ctx->rv.assigned, m * 4, hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(ctx, hipMemcpyAsync(ad.data(), ctx->rsv.rv.allocd, ad.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(ctx, hipMemcpyAsync(as.data(), ctx->rsv.rv.assigned, m * 4, hipMemcpyDeviceToHost, ctx->stream));
   HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
   for (int32_t i = 0; i < nr; ++i) {
-    const int32_t r = ctx->rsv_perm[i];
+    const int32_t r = ctx->rsv.perm[i];
     if (allocated)
       for (int d = 0; d < kRsvDims; ++d) allocated[(size_t)r * kRsvDims + d] = ad[(size_t)d * m + i];
     if (assigned) assigned[r] = as[i];
@@ -2959,14 +2992,14 @@ int ks_read_reservations(ks_ctx* ctx, int64_t* allocated, int32_t* assigned) {
 
 int ks_read_reservation_devices(ks_ctx* ctx, int64_t* dev_allocated) {
   if (!ctx) return KS_EINVAL;
-  const int32_t nr = ctx->rsv_live;
-  if (!dev_allocated || nr == 0 || !ctx->rsv_blob) return KS_OK;
-  const size_t m = (size_t)ctx->rv.nr;
+  const int32_t nr = ctx->rsv.live;
+  if (!dev_allocated || nr == 0 || !ctx->rsv.blob.get()) return KS_OK;
+  const size_t m = (size_t)ctx->rsv.rv.nr;
   std::vector<int64_t> dd((size_t)kDevQW * m);
-  HIPCHK(ctx, hipMemcpyAsync(dd.data(), ctx->rv.dald, dd.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(ctx, hipMemcpyAsync(dd.data(), ctx->rsv.rv.dald, dd.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
   HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
   for (int32_t i = 0; i < nr; ++i) {
-    const int32_t r = ctx->rsv_perm[(size_t)i];
+    const int32_t r = ctx->rsv.perm[(size_t)i];
     for (int w = 0; w < KS_DEV_WORDS; ++w) dev_allocated[(size_t)r * KS_DEV_WORDS + w] = dd[(size_t)w * m + i];
   }
   return KS_OK;
@@ -2975,46 +3008,47 @@ int ks_read_reservation_devices(ks_ctx* ctx, int64_t* dev_allocated) {
 int ks_update_nodes(ks_ctx* ctx, const int32_t* idx, const ks_node_cols* rows, int64_t m) {
   if (!ctx || !idx || !rows || m < 0) return ctx ? (ctx->err = "ks_update_nodes: bad args", KS_EINVAL) : KS_EINVAL;
   for (int64_t i = 0; ctx->cfg.numa.enable && rows->numa_flags && i < m; ++i)
-    if (idx[i] >= 0 && (size_t)idx[i] < ctx->h_dev_held.size() && ctx->h_dev_held[(size_t)idx[i]] &&
+    if (idx[i] >= 0 && (size_t)idx[i] < ctx->rsv.h_dev_held.size() && ctx->rsv.h_dev_held[(size_t)idx[i]] &&
         ((rows->numa_flags[i] >> KS_NUMA_POLICY_SHIFT) & 3u))
       KS_FAIL(ctx, KS_EUNSUPPORTED, "node %d: a NUMA topology policy on a node whose reservations hold devices", idx[i]);
-  if (!ctx->node_blob) KS_FAIL(ctx, KS_ESTATE, "ks_update_nodes before ks_load_nodes");
+  if (!ctx->nodes.blob.get()) KS_FAIL(ctx, KS_ESTATE, "ks_update_nodes before ks_load_nodes");
   if (m == 0) return KS_OK;
   for (int64_t i = 0; i < m; ++i)
-    if (idx[i] < 0 || idx[i] >= ctx->n) KS_FAIL(ctx, KS_EINVAL, "ks_update_nodes: idx[%lld]=%d out of range", (long long)i, idx[i]);
-  if (ctx->rsv_based) {
+    if (idx[i] < 0 || idx[i] >= ctx->nodes.n) KS_FAIL(ctx, KS_EINVAL, "ks_update_nodes: idx[%lld]=%d out of range", (long long)i, idx[i]);
+  if (ctx->rsv.based) {
     std::vector<int32_t> sorted(idx, idx + m);
     std::sort(sorted.begin(), sorted.end());
     if (std::adjacent_find(sorted.begin(), sorted.end()) != sorted.end())
       KS_FAIL(ctx, KS_EINVAL, "ks_update_nodes: duplicate node index with reservations loaded");
   }
   if (int rc = validate_nodes(ctx, rows, m); rc != KS_OK) return rc;
-  if (ctx->cfg.topology.enable && (rows->topo_nkeys != ctx->topo_nkeys || rows->topo_nprops != ctx->topo_nprops ||
-                                   rows->topo_ndomains > ctx->topo_ndom))
+  if (ctx->cfg.topology.enable && (rows->topo_nkeys != ctx->topo.nkeys || rows->topo_nprops != ctx->topo.nprops ||
+                                   rows->topo_ndomains > ctx->topo.ndom))
     KS_FAIL(ctx, KS_EINVAL, "ks_update_nodes: topology sizes differ from the loaded table's (%d keys, %d properties, "
-            "%d domains)", ctx->topo_nkeys, ctx->topo_nprops, ctx->topo_ndom);
+            "%d domains)", ctx->topo.nkeys, ctx->topo.nprops, ctx->topo.ndom);
   std::vector<const void*> src = host_cols(ctx, rows, m);
   std::vector<void*> dst;
   std::vector<int32_t> widths;
   std::vector<size_t> offs;
   size_t bytes = 0;
-  for (size_t i = 0; i < ctx->cols.size(); ++i) {
+  for (size_t i = 0; i < ctx->nodes.cols.size(); ++i) {
     if (!src[i]) continue;
-    dst.push_back(*ctx->cols[i].dev);
-    widths.push_back(ctx->cols[i].width);
+    dst.push_back(*ctx->nodes.cols[i].dev);
+    widths.push_back(ctx->nodes.cols[i].width);
     offs.push_back(bytes);
-    bytes += ((size_t)m * ctx->cols[i].width + 15) / 16 * 16;
+    bytes += ((size_t)m * ctx->nodes.cols[i].width + 15) / 16 * 16;
   }
   const size_t ncols = dst.size();
   const size_t meta = ncols * (sizeof(void*) * 2 + 4) + (size_t)m * 4 + 64;
   std::vector<char> host(bytes + meta);
-  void* dbuf = nullptr;
-  if (dev_alloc(ctx, &dbuf, bytes + meta) != KS_OK) return KS_ENOMEM;
+  DevPtr<> dbuf_owner;  // (freed on every way out)
+  if (dev_alloc(ctx, dbuf_owner, bytes + meta) != KS_OK) return KS_ENOMEM;
+  void* const dbuf = dbuf_owner.get();
   std::vector<const void*> srcdev(ncols);
   size_t j = 0;
-  for (size_t i = 0; i < ctx->cols.size(); ++i) {
+  for (size_t i = 0; i < ctx->nodes.cols.size(); ++i) {
     if (!src[i]) continue;
-    memcpy(host.data() + offs[j], src[i], (size_t)m * ctx->cols[i].width);
+    memcpy(host.data() + offs[j], src[i], (size_t)m * ctx->nodes.cols[i].width);
     srcdev[j] = (char*)dbuf + offs[j];
     ++j;
   }
@@ -3033,29 +3067,27 @@ int ks_update_nodes(ks_ctx* ctx, const int32_t* idx, const ks_node_cols* rows, i
                      (const int32_t*)((char*)dbuf + idx_off), m);
   HIPCHK(ctx, hipGetLastError());
   // the replaced rows are the reference's NodeInfo: add the reservation base restore again
-  if (ctx->rsv_based && rsv_launch_base(ctx, (const int32_t*)((char*)dbuf + idx_off), m, +1, 0) != KS_OK) return KS_EHIP;
+  if (ctx->rsv.based && rsv_launch_base(ctx, (const int32_t*)((char*)dbuf + idx_off), m, +1, 0) != KS_OK) return KS_EHIP;
   if (upload_prep_nodes(ctx) != KS_OK) return KS_EHIP;
   for (int64_t i = 0; ctx->cfg.numa.enable && rows->numa_flags && i < m; ++i) {
-    ctx->cpu_bind_labels |= ((rows->numa_flags[i] >> KS_NUMA_CPU_BIND_SHIFT) & 3u) != 0;
-    if ((size_t)idx[i] < ctx->h_pol.size()) ctx->h_pol[(size_t)idx[i]] = ((rows->numa_flags[i] >> KS_NUMA_POLICY_SHIFT) & 3u) != 0;
+    ctx->nodes.cpu_bind_labels |= ((rows->numa_flags[i] >> KS_NUMA_CPU_BIND_SHIFT) & 3u) != 0;
+    if ((size_t)idx[i] < ctx->nodes.h_pol.size()) ctx->nodes.h_pol[(size_t)idx[i]] = ((rows->numa_flags[i] >> KS_NUMA_POLICY_SHIFT) & 3u) != 0;
   }
   // (the union only grows: a stale bit only withholds the fast path from a pod)
-  for (int64_t i = 0; rows->taints_soft && i < m; ++i) ctx->soft_union |= rows->taints_soft[i];
+  for (int64_t i = 0; rows->taints_soft && i < m; ++i) ctx->nodes.soft_union |= rows->taints_soft[i];
   cores_mode(ctx);
   if (rows->numa_flags && cores_refresh(ctx) != KS_OK) return KS_EHIP;
   HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-  (void)hipFree(dbuf);
   return KS_OK;
 }
 
 int ks_load_quotas(ks_ctx* ctx, const ks_quota_cols* qc, int32_t nq) {
   if (!ctx || !qc || nq < 0) return ctx ? (ctx->err = "ks_load_quotas: bad args", KS_EINVAL) : KS_EINVAL;
   HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-  dev_free(ctx->quota_blob);
-  const size_t rows = (size_t)(nq > 0 ? nq : 1);
+  const size_t rows = (size_t)(nq > 0 ? nq : 1);  // (one row for an empty table)
   const size_t tbl = rows * KS_QUOTA_DIMS * 8;
   const size_t bytes = rows * 12 + 16 + tbl * 6;
-  if (dev_alloc(ctx, &ctx->quota_blob, bytes) != KS_OK) return KS_ENOMEM;
+  if (dev_alloc(ctx, ctx->quota.blob, bytes) != KS_OK) return KS_ENOMEM;
   std::vector<char> h(bytes, 0);
   char* b = h.data();
   int32_t* parent = (int32_t*)b;
@@ -3087,25 +3119,24 @@ int ks_load_quotas(ks_ctx* ctx, const ks_quota_cols* qc, int32_t nq) {
   }
   // the table is valid: a blob of its size for it (the one allocated above is released again); a table refused
   // above has already replaced the loaded one's blob, so load a valid table before scheduling (include/koordgpu.h)
-  dev_free(ctx->quota_blob);
-  if (dev_alloc(ctx, &ctx->quota_blob, bytes) != KS_OK) {
-    ctx->q = DevQuotas{};
+  if (dev_alloc(ctx, ctx->quota.blob, bytes) != KS_OK) {
+    ctx->quota.q = DevQuotas{};
     return KS_ENOMEM;
   }
   // a staged batch's quota rows were checked against the old row count (validate_pods)
-  if (ctx->np > 0 && nq < ctx->q.q) ctx->staged_stale = true;
-  HIPCHK(ctx, hipMemcpyAsync(ctx->quota_blob, h.data(), bytes, hipMemcpyHostToDevice, ctx->stream));
-  char* d = (char*)ctx->quota_blob;
-  ctx->q.q = nq;
-  ctx->q.parent = (int32_t*)d;
-  ctx->q.limit_mask = (uint32_t*)(d + rows * 4);
-  ctx->q.min_mask = (uint32_t*)(d + rows * 8);
-  ctx->q.limit = (int64_t*)(d + toff);
-  ctx->q.used = ctx->q.limit + rows * KS_QUOTA_DIMS;
-  ctx->q.min = ctx->q.used + rows * KS_QUOTA_DIMS;
-  ctx->q.npused = ctx->q.min + rows * KS_QUOTA_DIMS;
-  ctx->quota_used_ckpt = ctx->q.npused + rows * KS_QUOTA_DIMS;
-  ctx->quota_npused_ckpt = ctx->quota_used_ckpt + rows * KS_QUOTA_DIMS;
+  if (ctx->staged.np > 0 && nq < ctx->quota.q.q) ctx->staged.stale = true;
+  HIPCHK(ctx, hipMemcpyAsync(ctx->quota.blob.get(), h.data(), bytes, hipMemcpyHostToDevice, ctx->stream));
+  char* d = (char*)ctx->quota.blob.get();
+  ctx->quota.q.q = nq;
+  ctx->quota.q.parent = (int32_t*)d;
+  ctx->quota.q.limit_mask = (uint32_t*)(d + rows * 4);
+  ctx->quota.q.min_mask = (uint32_t*)(d + rows * 8);
+  ctx->quota.q.limit = (int64_t*)(d + toff);
+  ctx->quota.q.used = ctx->quota.q.limit + rows * KS_QUOTA_DIMS;
+  ctx->quota.q.min = ctx->quota.q.used + rows * KS_QUOTA_DIMS;
+  ctx->quota.q.npused = ctx->quota.q.min + rows * KS_QUOTA_DIMS;
+  ctx->quota.snap[0] = Snap{ctx->quota.q.used, ctx->quota.q.npused + rows * KS_QUOTA_DIMS, tbl};
+  ctx->quota.snap[1] = Snap{ctx->quota.q.npused, ctx->quota.q.npused + 2 * rows * KS_QUOTA_DIMS, tbl};
   HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
   return KS_OK;
 }
@@ -3185,8 +3216,9 @@ int ks_refresh_quota_runtime(ks_ctx* ctx, const ks_quota_tree* t, int32_t nq, in
   h32.resize(h32.size() + (nq + 3) / 4, 0);
   memcpy(h32.data() + o_al, std::vector<uint8_t>(al.begin(), al.end()).data(), nq);
   const size_t b64 = h64.size() * 8, b32 = h32.size() * 4;
-  void* dbuf = nullptr;
-  if (dev_alloc(ctx, &dbuf, b64 + b32) != KS_OK) return KS_ENOMEM;
+  DevPtr<> dbuf_owner;  // (freed on every way out)
+  if (dev_alloc(ctx, dbuf_owner, b64 + b32) != KS_OK) return KS_ENOMEM;
+  void* const dbuf = dbuf_owner.get();
   HIPCHK(ctx, hipMemcpyAsync(dbuf, h64.data(), b64, hipMemcpyHostToDevice, ctx->stream));
   HIPCHK(ctx, hipMemcpyAsync((char*)dbuf + b64, h32.data(), b32, hipMemcpyHostToDevice, ctx->stream));
   const int64_t* d64 = (const int64_t*)dbuf;
@@ -3213,10 +3245,7 @@ int ks_refresh_quota_runtime(ks_ctx* ctx, const ks_quota_tree* t, int32_t nq, in
   // one wave per dimension; as many dimensions per launch as LDS holds (3 x int64 per quota)
   const size_t per_dim = (size_t)nq * 3 * 8;
   int dims_per = (int)std::min<size_t>(D, kLdsBytes / per_dim);
-  if (dims_per < 1) {
-    (void)hipFree(dbuf);
-    KS_FAIL(ctx, KS_EUNSUPPORTED, "quota tree too large for the runtime kernel's LDS (%d quotas)", nq);
-  }
+  if (dims_per < 1) KS_FAIL(ctx, KS_EUNSUPPORTED, "quota tree too large for the runtime kernel's LDS (%d quotas)", nq);
   hipError_t e = hipFuncSetAttribute((const void*)quota_runtime_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
                                      (int)(per_dim * dims_per));
   for (int d0 = 0; e == hipSuccess && d0 < D; d0 += dims_per) {
@@ -3227,14 +3256,14 @@ int ks_refresh_quota_runtime(ks_ctx* ctx, const ks_quota_tree* t, int32_t nq, in
   }
   if (e == hipSuccess) e = hipMemcpyAsync(rtout, qa.runtime, tbl * 8, hipMemcpyDeviceToHost, ctx->stream);
   // install as the admission limit of the loaded quota table (EnableRuntimeQuota)
-  if (e == hipSuccess && ctx->quota_blob && ctx->q.q == nq) {
-    e = hipMemcpyAsync(ctx->q.limit, qa.runtime, tbl * 8, hipMemcpyDeviceToDevice, ctx->stream);
+  if (e == hipSuccess && ctx->quota.blob.get() && ctx->quota.q.q == nq) {
+    e = hipMemcpyAsync(ctx->quota.q.limit, qa.runtime, tbl * 8, hipMemcpyDeviceToDevice, ctx->stream);
     std::vector<uint32_t> lm(nq, keys);
-    if (e == hipSuccess) e = hipMemcpyAsync(ctx->q.limit_mask, lm.data(), (size_t)nq * 4, hipMemcpyHostToDevice, ctx->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(ctx->quota.q.limit_mask, lm.data(), (size_t)nq * 4, hipMemcpyHostToDevice, ctx->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
   }
   if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-  (void)hipFree(dbuf);
+  dbuf_owner.reset();
   if (e != hipSuccess) KS_FAIL(ctx, KS_EHIP, "ks_refresh_quota_runtime: %s", hipGetErrorString(e));
   if (runtime) memcpy(runtime, rtout, tbl * 8);
   if (runtime_mask)
@@ -3247,8 +3276,7 @@ int ks_refresh_quota_runtime(ks_ctx* ctx, const ks_quota_tree* t, int32_t nq, in
 // ks_schedule_staged (PreFilter / EstimatePod work is part of the scheduling call); single-pod evaluation has its
 // own stage (ctx->est) so it never disturbs staged pods.
 static int ensure_stage(ks_ctx* ctx, PodStage& st, int32_t p) {
-  if (p <= st.cap && st.blob) return KS_OK;
-  dev_free(st.blob);
+  if (p <= st.cap && st.blob.get()) return KS_OK;
   st.cap = 0;
   const int32_t cap = std::max<int32_t>(p, 64);
   const size_t rec = (size_t)cap * sizeof(PodRec);
@@ -3259,8 +3287,8 @@ static int ensure_stage(ks_ctx* ctx, PodStage& st, int32_t p) {
   // cpu_bind joint(u8) = 6 x32
   const size_t pst = (size_t)cap * sizeof(PodStat);
   const size_t bytes = rec + pst + res + col8 * 27 + col4 * 7;
-  if (dev_alloc(ctx, &st.blob, bytes) != KS_OK) return KS_ENOMEM;
-  char* b = (char*)st.blob;
+  if (dev_alloc(ctx, st.blob, bytes) != KS_OK) return KS_ENOMEM;
+  char* b = (char*)st.blob.get();
   st.recs = (PodRec*)b;
   b += rec;
   st.stat = (PodStat*)b;
@@ -3303,16 +3331,14 @@ static int ensure_stage(ks_ctx* ctx, PodStage& st, int32_t p) {
 // int64 columns, then 7 x 32-bit ones, each st.col8 / st.col4 bytes apart) and copied once.
 static int stage_cols_packed(ks_ctx* ctx, PodStage& st, const ks_pod_cols* pc, int32_t p) {
   const size_t bytes = st.col8 * 27 + st.col4 * 7;
-  if (!st.h_pack || st.pack_bytes < bytes) {
-    if (st.h_pack) (void)hipHostFree(st.h_pack);
-    st.h_pack = nullptr;
+  if (!st.h_pack.get() || st.pack_bytes < bytes) {
     st.pack_bytes = 0;
-    HIPCHK(ctx, hipHostMalloc(&st.h_pack, bytes, hipHostMallocDefault));
+    if (int rc = host_alloc(ctx, st.h_pack, bytes); rc != KS_OK) return rc;
     st.pack_bytes = bytes;
   }
   // the previous call's copy out of the pinned buffer must be done before it is rewritten
   HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-  unsigned char* h = (unsigned char*)st.h_pack;
+  unsigned char* h = (unsigned char*)st.h_pack.get();
   const int64_t* c8[27] = {pc->req_milli_cpu, pc->req_memory, pc->req_ephemeral, pc->nonzero_milli_cpu, pc->nonzero_memory,
                            pc->req_scalar[0], pc->req_scalar[1], pc->req_scalar[2], pc->req_scalar[3], pc->la_req_cpu,
                            pc->la_lim_cpu, pc->la_dflt_cpu, pc->la_req_memory, pc->la_lim_memory, pc->la_dflt_memory,
@@ -3387,10 +3413,8 @@ static int stage_cols(ks_ctx* ctx, PodStage& st, const ks_pod_cols* pc, int32_t 
   if (ctx->cfg.topology.enable) {
     const int64_t nt = (pc->topo_term_beg && pc->topo_terms) ? pc->topo_term_beg[p] : 0;
     const int64_t npr = (pc->topo_prop_beg && pc->topo_props) ? pc->topo_prop_beg[p] : 0;
-    auto grow = [&](void** buf, int64_t& cap, int64_t want, size_t elem) -> int {
-      if (want <= cap && *buf) return KS_OK;
-      dev_free(*buf);
-      *buf = nullptr;
+    auto grow = [&](auto& buf, int64_t& cap, int64_t want, size_t elem) -> int {
+      if (want <= cap && buf.get()) return KS_OK;
       cap = 0;
       const int64_t c = std::max<int64_t>(want, 64);
       if (dev_alloc(ctx, buf, (size_t)c * elem) != KS_OK) return KS_ENOMEM;
@@ -3398,8 +3422,8 @@ static int stage_cols(ks_ctx* ctx, PodStage& st, const ks_pod_cols* pc, int32_t 
       return KS_OK;
     };
     int64_t rcap = st.topo_cap;
-    if (grow((void**)&st.topo, rcap, p, sizeof(TopoRec)) != KS_OK || grow((void**)&st.topo_terms, st.topo_tcap, nt, 8) != KS_OK ||
-        grow((void**)&st.topo_props, st.topo_pcap, npr, 4) != KS_OK)
+    if (grow(st.topo, rcap, p, sizeof(TopoRec)) != KS_OK || grow(st.topo_terms, st.topo_tcap, nt, 8) != KS_OK ||
+        grow(st.topo_props, st.topo_pcap, npr, 4) != KS_OK)
       return KS_ENOMEM;
     st.topo_cap = (int32_t)rcap;
     std::vector<TopoRec>& ht = st.h_topo;
@@ -3418,10 +3442,10 @@ static int stage_cols(ks_ctx* ctx, PodStage& st, const ks_pod_cols* pc, int32_t 
       if (r.nterms == 0) r.flags &= ~KS_TOPO_DYN;  // (no query term: nothing the step would ask)
       st.ndyn += (r.flags & KS_TOPO_DYN) ? 1 : 0;
     }
-    if (p > 0) HIPCHK(ctx, hipMemcpyAsync(st.topo, ht.data(), (size_t)p * sizeof(TopoRec), hipMemcpyHostToDevice, ctx->stream));
-    if (nt) HIPCHK(ctx, hipMemcpyAsync(st.topo_terms, pc->topo_terms, (size_t)nt * 8, hipMemcpyHostToDevice, ctx->stream));
-    if (npr) HIPCHK(ctx, hipMemcpyAsync(st.topo_props, pc->topo_props, (size_t)npr * 4, hipMemcpyHostToDevice, ctx->stream));
-    st.cols.topo = st.topo;
+    if (p > 0) HIPCHK(ctx, hipMemcpyAsync(st.topo.get(), ht.data(), (size_t)p * sizeof(TopoRec), hipMemcpyHostToDevice, ctx->stream));
+    if (nt) HIPCHK(ctx, hipMemcpyAsync(st.topo_terms.get(), pc->topo_terms, (size_t)nt * 8, hipMemcpyHostToDevice, ctx->stream));
+    if (npr) HIPCHK(ctx, hipMemcpyAsync(st.topo_props.get(), pc->topo_props, (size_t)npr * 4, hipMemcpyHostToDevice, ctx->stream));
+    st.cols.topo = st.topo.get();
   }
   if (ctx->kc.stat || ctx->cfg.topology.enable) {
     std::vector<PodStat>& hs = st.h_stat;
@@ -3432,7 +3456,7 @@ static int stage_cols(ks_ctx* ctx, PodStage& st, const ks_pod_cols* pc, int32_t 
       PodStat& r = hs[(size_t)i];
       r.tol = pc->tolerated ? pc->tolerated[i] : 0;
       r.nreq = pc->affinity_required_n ? pc->affinity_required_n[i] : 0;
-      bool dyn = (ctx->kc.taint & 2) && (ctx->soft_union & ~r.tol) != 0;
+      bool dyn = (ctx->kc.taint & 2) && (ctx->nodes.soft_union & ~r.tol) != 0;
       for (int t = 0; t < KS_AFFINITY_TERMS; ++t) {
         r.req[t] = pc->affinity_required[t] ? pc->affinity_required[t][i] : 0;
         r.pref[t] = pc->affinity_preferred[t] ? pc->affinity_preferred[t][i] : 0;
@@ -3480,7 +3504,7 @@ static int validate_pods(ks_ctx* ctx, const ks_pod_cols* pc, int32_t p) {
         const uint64_t w = pc->topo_terms[t];
         const int kind = (int)(w & 0xF), key = (int)((w >> 8) & 0xFF), prop = (int)((w >> 16) & 0xFFFF);
         const int32_t param = (int32_t)(uint32_t)(w >> 32);
-        if (kind < KS_TOPO_K_SPREAD_HARD || kind > KS_TOPO_K_SCORE || prop >= ctx->topo_nprops || key > ctx->topo_nkeys ||
+        if (kind < KS_TOPO_K_SPREAD_HARD || kind > KS_TOPO_K_SCORE || prop >= ctx->topo.nprops || key > ctx->topo.nkeys ||
             ((w >> 5) & 0x7) != 0 ||
             ((kind == KS_TOPO_K_SPREAD_HARD || kind == KS_TOPO_K_SPREAD_SOFT) && param < 1) ||
             (kind == KS_TOPO_K_SCORE && (param < -1000000 || param > 1000000)))
@@ -3491,8 +3515,8 @@ static int validate_pods(ks_ctx* ctx, const ks_pod_cols* pc, int32_t p) {
       const int32_t b = pc->topo_prop_beg[i], e = pc->topo_prop_beg[i + 1];
       if ((i == 0 && b != 0) || e < b) KS_FAIL(ctx, KS_EINVAL, "pod %d: topology property offsets [%d, %d)", i, b, e);
       for (int32_t k = b; k < e; ++k)
-        if (pc->topo_props[k] < 0 || pc->topo_props[k] >= ctx->topo_nprops)
-          KS_FAIL(ctx, KS_EINVAL, "pod %d: topology property %d outside [0, %d)", i, pc->topo_props[k], ctx->topo_nprops);
+        if (pc->topo_props[k] < 0 || pc->topo_props[k] >= ctx->topo.nprops)
+          KS_FAIL(ctx, KS_EINVAL, "pod %d: topology property %d outside [0, %d)", i, pc->topo_props[k], ctx->topo.nprops);
     }
   }
   for (int32_t i = 0; pc->flags && i < p; ++i)
@@ -3547,13 +3571,13 @@ static int validate_pods(ks_ctx* ctx, const ks_pod_cols* pc, int32_t p) {
   }
   if (pc->quota) {
     for (int32_t i = 0; i < p; ++i)
-      if (pc->quota[i] >= ctx->q.q || pc->quota[i] < -1)
-        KS_FAIL(ctx, KS_EINVAL, "pod %d: quota row %d out of range (loaded %d)", i, pc->quota[i], ctx->q.q);
+      if (pc->quota[i] >= ctx->quota.q.q || pc->quota[i] < -1)
+        KS_FAIL(ctx, KS_EINVAL, "pod %d: quota row %d out of range (loaded %d)", i, pc->quota[i], ctx->quota.q.q);
   }
   // a pod requesting a scalar slot no node advertises still has to be evaluated against the
   // (zero) allocatable of that slot: widen the kernels' scalar template to cover it
-  int need = ctx->nsc;
-  for (int k = ctx->nsc; k < KS_MAX_SCALARS; ++k) {
+  int need = ctx->nodes.nsc;
+  for (int k = ctx->nodes.nsc; k < KS_MAX_SCALARS; ++k) {
     if (!pc->req_scalar[k]) continue;
     for (int32_t i = 0; i < p; ++i)
       if (pc->req_scalar[k][i] != 0) {
@@ -3561,50 +3585,50 @@ static int validate_pods(ks_ctx* ctx, const ks_pod_cols* pc, int32_t p) {
         break;
       }
   }
-  if (need > ctx->nsc) {
-    ctx->nsc = need <= 2 ? 2 : 4;
-    ctx->kc.nsc = ctx->nsc;
+  if (need > ctx->nodes.nsc) {
+    ctx->nodes.nsc = need <= 2 ? 2 : 4;
+    ctx->kc.nsc = ctx->nodes.nsc;
   }
   // only a batch (or pod) that passed every check decides the core-count mode, and only for its own operation
   // (bind_mode): a rejected or probed pod leaves later schedules as they were
-  ctx->val_bind_required = any_req;
+  ctx->staged.val_bind_required = any_req;
   return KS_OK;
 }
 
 // Cfg.cores for the operation about to run: node CPU bind labels, or a required policy among its pods
 static void bind_mode(ks_ctx* ctx, bool required) {
-  ctx->cpu_bind_required = required;
+  ctx->staged.cpu_bind_required = required;
   cores_mode(ctx);
 }
 
 int ks_stage_pods(ks_ctx* ctx, const ks_pod_cols* pods, int32_t p) {
   if (!ctx || !pods || p < 0) return ctx ? (ctx->err = "ks_stage_pods: bad args", KS_EINVAL) : KS_EINVAL;
-  if (!ctx->node_blob) KS_FAIL(ctx, KS_ESTATE, "ks_stage_pods before ks_load_nodes");
+  if (!ctx->nodes.blob.get()) KS_FAIL(ctx, KS_ESTATE, "ks_stage_pods before ks_load_nodes");
   KS_NOM_REFUSE(ctx, "ks_stage_pods / ks_schedule");
-  if (ctx->cfg.quota.enable && pods->quota && !ctx->quota_blob)
+  if (ctx->cfg.quota.enable && pods->quota && !ctx->quota.blob.get())
     KS_FAIL(ctx, KS_ESTATE, "ElasticQuota enabled but ks_load_quotas not called");
   if (int rc = validate_pods(ctx, pods, p); rc != KS_OK) return rc;
   HIPCHK(ctx, hipSetDevice(ctx->device));
   if (ensure_stage(ctx, ctx->st, p) != KS_OK) return KS_ENOMEM;
   if (p > 0 && stage_cols(ctx, ctx->st, pods, p) != KS_OK) return KS_EHIP;
-  ctx->np = p;
-  ctx->staged_stale = false;
-  ctx->staged_bind_required = ctx->val_bind_required;
+  ctx->staged.np = p;
+  ctx->staged.stale = false;
+  ctx->staged.bind_required = ctx->staged.val_bind_required;
   HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
   return KS_OK;
 }
 
 static hipEvent_t take_event(ks_ctx* ctx, size_t i) {
   while (ctx->ev_pool.size() <= i) {
-    hipEvent_t e;
-    if (hipEventCreate(&e) != hipSuccess) return nullptr;
-    ctx->ev_pool.push_back(e);
+    Event e;
+    if (hipEventCreate(&e.h) != hipSuccess) return nullptr;
+    ctx->ev_pool.push_back(std::move(e));
   }
   return ctx->ev_pool[i];
 }
 
 // the kernel variant the context's plugins select (ks_plan.h), for the paths that run without a commit plan
-static int kernel_feat(const ks_ctx* ctx) { return plan_feat(ctx->kc, ctx->dev_held_any); }
+static int kernel_feat(const ks_ctx* ctx) { return plan_feat(ctx->kc, ctx->rsv.dev_held_any); }
 
 // the launch wrappers of the FEAT variant (ks_variant.hip)
 // wide: the context's NUMA width is kNumaWide (only the NUMA topology policy plugin sets have such kernels)
@@ -3626,7 +3650,7 @@ static PassLaunch pass_launcher(int feat, int nsc, bool wide) {
 #undef KS_PICK
 }
 
-// The commit kernel's arguments for the pods of stage st (cursor ctx->cursor, `total` pods, `batch` per pass).
+// The commit kernel's arguments for the pods of stage st (cursor ctx->cursor.get(), `total` pods, `batch` per pass).
 // Candidate-list set i (0 or 1) of the context's double buffer; set 0 unless passes are pipelined.
 struct CandSet {
   uint32_t* chunk;
@@ -3636,61 +3660,61 @@ struct CandSet {
 };
 static CandSet cand_set(const ks_ctx* ctx, int i) {
   const size_t e = (size_t)i * kMaxBatch * kMaxCand, r = (size_t)i * kMaxBatch;
-  return CandSet{ctx->cand_chunk + e, ctx->cand_t + e, ctx->cand_bound + r, ctx->cand_top + r, ctx->cand_second + r,
-                 ctx->cand_count + r, ctx->cand_total + r};
+  return CandSet{ctx->cand_chunk.get() + e, ctx->cand_t.get() + e, ctx->cand_bound.get() + r, ctx->cand_top.get() + r, ctx->cand_second.get() + r,
+                 ctx->cand_count.get() + r, ctx->cand_total.get() + r};
 }
 
 static CommitArgs commit_args(ks_ctx* ctx, PodStage& st, int32_t total, int32_t batch) {
   const CommitPlan& plan = ctx->plan;
   CommitArgs ca;
-  ca.dn = ctx->dnodes;
-  ca.rv = ctx->drv;
+  ca.dn = ctx->dnodes.get();
+  ca.rv = ctx->drv.get();
   ca.c = ctx->kc;
   ca.pods = st.recs;
   ca.pstat = st.stat;
   ca.pq = st.pq;
-  ca.q = ctx->q;
-  ca.cursor = ctx->cursor;
-  ca.cand_chunk = ctx->cand_chunk;
-  ca.cand_t = ctx->cand_t;
-  ca.cand_bound = ctx->cand_bound;
-  ca.cand_top = ctx->cand_top;
-  ca.cand_second = ctx->cand_second;
-  ca.cand_count = ctx->cand_count;
+  ca.q = ctx->quota.q;
+  ca.cursor = ctx->cursor.get();
+  ca.cand_chunk = ctx->cand_chunk.get();
+  ca.cand_t = ctx->cand_t.get();
+  ca.cand_bound = ctx->cand_bound.get();
+  ca.cand_top = ctx->cand_top.get();
+  ca.cand_second = ctx->cand_second.get();
+  ca.cand_count = ctx->cand_count.get();
   ca.results = st.results;
-  ca.counters = ctx->counters;
-  ca.n = ctx->n;
-  ca.nchunks = ctx->nchunks;
+  ca.counters = ctx->counters.get();
+  ca.n = ctx->nodes.n;
+  ca.nchunks = ctx->nodes.nchunks;
   ca.total_pods = total;
   ca.batch = batch;
   ca.k = ctx->k;
-  ca.rowcols = ctx->rowcols;
+  ca.rowcols = ctx->rowcols.get();
   ca.rcap = plan.rcap;
   ca.rsv_bytes = (int32_t)plan.rsv_bytes;
   ca.dev_bytes = (int32_t)plan.dev_bytes;
   ca.stat_lds = plan.stat_lds ? 1 : 0;
-  ca.dv = ctx->ddv;
-  ca.dev_M = ctx->dev_M;
-  ca.cpuset_list = ctx->cpuset_list;
+  ca.dv = ctx->ddv.get();
+  ca.dev_M = ctx->dev_M.get();
+  ca.cpuset_list = ctx->cpuset_list.get();
   ca.cpuset_n = ctx->cpuset_n;
   ca.cpuset_split = ctx->cpuset_split;
   ca.numa_alloc = ctx->numa_alloc;
   ca.force = 0;
   ca.numa_bytes = (int32_t)plan.numa_bytes;
-  ca.nv = ctx->dnv;
+  ca.nv = ctx->dnv.get();
   ca.pipe_base = nullptr;
   ca.carry = nullptr;
   ca.pipe_follow = nullptr;
   ca.pipe_after = nullptr;
   ca.top_reset = nullptr;
   ca.pre_rsv = nullptr;
-  ca.topo = ctx->cfg.topology.enable && st.topo ? 1 : 0;
+  ca.topo = ctx->cfg.topology.enable && st.topo.get() ? 1 : 0;
   ca.topo_const = (int32_t)(100 * ctx->cfg.topology.spread_weight);
-  ca.topo_rec = st.topo;
-  ca.topo_props = st.topo_props;
-  ca.topo_count = ctx->topo_count;
-  ca.topo_npad = ctx->npad;
-  ca.topo_best = ctx->topo_scr ? &ctx->topo_scr->best_total : nullptr;
+  ca.topo_rec = st.topo.get();
+  ca.topo_props = st.topo_props.get();
+  ca.topo_count = ctx->topo.count;
+  ca.topo_npad = ctx->nodes.npad;
+  ca.topo_best = ctx->topo.scr ? &ctx->topo.scr->best_total : nullptr;
   return ca;
 }
 
@@ -3704,11 +3728,11 @@ static int commit_attr_set(ks_ctx* ctx) {
   CommitPlanIn in{};
   in.kc = ctx->kc;
   in.k_cfg = ctx->k_cfg;
-  in.nchunks = ctx->nchunks;
-  in.nsc = ctx->nsc;
-  in.numa_w = ctx->numa_w;
-  in.q = ctx->q.q;
-  in.dev_held_any = ctx->dev_held_any;
+  in.nchunks = ctx->nodes.nchunks;
+  in.nsc = ctx->nodes.nsc;
+  in.numa_w = ctx->numa.w;
+  in.q = ctx->quota.q.q;
+  in.dev_held_any = ctx->rsv.dev_held_any;
   in.commit_fq = ctx->commit_fq;
   in.fq_keys = ctx->fq_keys;
   in.general_mode = (int)env_general;
@@ -3719,15 +3743,15 @@ static int commit_attr_set(ks_ctx* ctx) {
             "reservations holding devices together with a NUMA-policy node with more than %d NUMA nodes", kNumaDev);
   ctx->k = plan.k;
   if (plan.status == PlanStatus::kTooLarge)
-    KS_FAIL(ctx, KS_EUNSUPPORTED, "too many nodes for the commit kernel's LDS (%lld nodes, %zu B)", (long long)ctx->n, plan.smem);
-  hipError_t e = pass_launcher(plan.feat, ctx->nsc, plan.wide).commit_attr(plan.qcache, plan.smem);
+    KS_FAIL(ctx, KS_EUNSUPPORTED, "too many nodes for the commit kernel's LDS (%lld nodes, %zu B)", (long long)ctx->nodes.n, plan.smem);
+  hipError_t e = pass_launcher(plan.feat, ctx->nodes.nsc, plan.wide).commit_attr(plan.qcache, plan.smem);
   if (e != hipSuccess) KS_FAIL(ctx, KS_EHIP, "hipFuncSetAttribute(commit LDS %zu): %s", plan.smem, hipGetErrorString(e));
   if (plan.fq) {
-    e = fq_launcher(ctx->nsc).commit_attr(plan.fq_keys, plan.fq_smem);
+    e = fq_launcher(ctx->nodes.nsc).commit_attr(plan.fq_keys, plan.fq_smem);
     if (e != hipSuccess) KS_FAIL(ctx, KS_EHIP, "hipFuncSetAttribute(fq commit LDS %zu): %s", plan.fq_smem, hipGetErrorString(e));
   }
   if (plan.mono) {
-    e = pass_launcher(0, ctx->nsc, false).commit_mono_attr(plan.qcache, plan.mono_smem);
+    e = pass_launcher(0, ctx->nodes.nsc, false).commit_mono_attr(plan.qcache, plan.mono_smem);
     if (e != hipSuccess)
       KS_FAIL(ctx, KS_EHIP, "hipFuncSetAttribute(mono commit LDS %zu): %s", plan.mono_smem, hipGetErrorString(e));
   }
@@ -3737,14 +3761,11 @@ static int commit_attr_set(ks_ctx* ctx) {
 // (pod, node) list + count + per-pod CPU sets / NUMA split / NUMA allocation of one call, for np pods
 static int ensure_cpuset_bufs(ks_ctx* ctx, int32_t np) {
   if (!ctx->cfg.numa.enable || ctx->cpuset_cap >= np) return KS_OK;
-  void* p = ctx->cpuset_list;
-  dev_free(p);
-  ctx->cpuset_list = nullptr;
   const int32_t cap = std::max<int32_t>(np, 64);
   const size_t o_n = (size_t)cap * 8, o_out = o_n + 16, o_split = o_out + (size_t)cap * sizeof(CpuSet),
                o_alloc = align16(o_split + (size_t)cap * 8), bytes = o_alloc + (size_t)cap * 2 * kNumaWide * 8;  // (either width)
-  if (dev_alloc(ctx, &p, bytes) != KS_OK) return KS_ENOMEM;
-  ctx->cpuset_list = (int2*)p;
+  if (dev_alloc(ctx, ctx->cpuset_list, bytes) != KS_OK) return KS_ENOMEM;
+  char* const p = (char*)ctx->cpuset_list.get();
   ctx->cpuset_n = (int32_t*)((char*)p + o_n);
   ctx->cpuset_out = (CpuSet*)((char*)p + o_out);
   ctx->cpuset_split = (uint32_t*)((char*)p + o_split);
@@ -3768,7 +3789,7 @@ static bool pipelined(const ks_ctx* ctx) {
   const int feat = kernel_feat(ctx);
   if (mode == 0 || !(feat == 0 || feat == 1) || ctx->kc.dev || ctx->kc.cores) return false;
   if (ctx->cfg.topology.enable && ctx->st.ndyn > 0) return false;  // topology pods: the topology step between passes
-  return mode == 2 || ctx->n >= env_min;
+  return mode == 2 || ctx->nodes.n >= env_min;
 }
 
 // The pipelined passes' two streams per device, shared by the process's contexts for the life of the process
@@ -3798,12 +3819,9 @@ static void release_pipe_streams() {
 // commit and the patched passes' list re-evaluation never share a CU with sweep waves; KS_PIPE_CUMASK=0: no masks), the
 // pipe words and the event ring.
 static int ensure_pipe(ks_ctx* ctx) {
-  if (!ctx->pipe) {
-    void* p = nullptr;
-    if (dev_alloc(ctx, &p, kPipeWords * 4) != KS_OK) return KS_ENOMEM;
-    ctx->pipe = (int32_t*)p;
-    if (dev_alloc(ctx, &p, 2 * kMaxBatch * 8) != KS_OK) return KS_ENOMEM;
-    ctx->pipe_top = (unsigned long long*)p;
+  if (!ctx->pipe.get()) {
+    if (dev_alloc(ctx, ctx->pipe, kPipeWords * 4) != KS_OK) return KS_ENOMEM;
+    if (dev_alloc(ctx, ctx->pipe_top, 2 * kMaxBatch * 8) != KS_OK) return KS_ENOMEM;
   }
   if (!ctx->sstream) {
     // One sweep stream and one commit stream per device for the whole process, shared by every context: a
@@ -3845,8 +3863,8 @@ static int ensure_pipe(ks_ctx* ctx) {
     ctx->cstream = st.c ? st.c : ctx->stream;
   }
   for (int i = 0; i < kPipeEvents; ++i) {
-    if (!ctx->pev_sel[i]) HIPCHK(ctx, hipEventCreateWithFlags(&ctx->pev_sel[i], hipEventDisableTiming));
-    if (!ctx->pev_com[i]) HIPCHK(ctx, hipEventCreateWithFlags(&ctx->pev_com[i], hipEventDisableTiming));
+    if (!ctx->pev_sel[i]) HIPCHK(ctx, hipEventCreateWithFlags(&ctx->pev_sel[i].h, hipEventDisableTiming));
+    if (!ctx->pev_com[i]) HIPCHK(ctx, hipEventCreateWithFlags(&ctx->pev_com[i].h, hipEventDisableTiming));
   }
   return KS_OK;
 }
@@ -3911,10 +3929,10 @@ static int loop_exchange(ks_ctx* ctx, hipStream_t s, Pull pull) {
 static int exchange_allgather(ks_ctx* ctx, size_t bytes, hipStream_t s) {
   if (ctx->loop)
     return loop_exchange(ctx, s, [&](ks_ctx* peer, int32_t p) {
-      return hipMemcpyAsync(ctx->gather + (size_t)p * bytes, peer->gather + (size_t)p * bytes, bytes,
+      return hipMemcpyAsync(ctx->gather.get() + (size_t)p * bytes, peer->gather.get() + (size_t)p * bytes, bytes,
                             hipMemcpyDeviceToDevice, s);
     });
-  const ncclResult_t r = ncclAllGather(ctx->gather + (size_t)ctx->rank * bytes, ctx->gather, bytes, ncclUint8, ctx->comm, s);
+  const ncclResult_t r = ncclAllGather(ctx->gather.get() + (size_t)ctx->rank * bytes, ctx->gather.get(), bytes, ncclUint8, ctx->comm, s);
   if (r != ncclSuccess) KS_FAIL(ctx, KS_EHIP, "ncclAllGather (candidate slots): %s", ncclGetErrorString(r));
   return KS_OK;
 }
@@ -3929,17 +3947,17 @@ __global__ void max_reduce_kernel(unsigned long long* buf, const unsigned long l
   buf[i] = m;
 }
 
-// In-place max all-reduce of the pass's normalization maxima (count u64 words at buf = ctx->dev_M).
+// In-place max all-reduce of the pass's normalization maxima (count u64 words at buf = ctx->dev_M.get()).
 static int exchange_allreduce_max(ks_ctx* ctx, unsigned long long* buf, int32_t count, hipStream_t s) {
   if (ctx->loop) {
     if (int rc = loop_exchange(ctx, s, [&](ks_ctx* peer, int32_t p) {
-          return hipMemcpyAsync(ctx->loop_scratch + (size_t)p * count, peer->dev_M, (size_t)count * 8,
+          return hipMemcpyAsync(ctx->loop_scratch.get() + (size_t)p * count, peer->dev_M.get(), (size_t)count * 8,
                                 hipMemcpyDeviceToDevice, s);
         });
         rc != KS_OK)
       return rc;
     hipLaunchKernelGGL(max_reduce_kernel, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, s, buf,
-                       (const unsigned long long*)ctx->loop_scratch, ctx->nranks, ctx->rank, count);
+                       (const unsigned long long*)ctx->loop_scratch.get(), ctx->nranks, ctx->rank, count);
     HIPCHK(ctx, hipGetLastError());
     return KS_OK;
   }
@@ -3964,15 +3982,14 @@ struct EvBuf {
   int32_t *draw, *dhi, *ddraw, *dtraw, *daraw;
 };
 static int ev_buffers(ks_ctx* ctx, EvBuf& b) {
-  const int64_t n = ctx->n;
+  const int64_t n = ctx->nodes.n;
   const size_t bytes = (size_t)(n > 0 ? n : 1) * (4 + 8 * KS_NUM_SCORE_PLUGINS + 8 + 8 + 4 + 8) + 64;
   if (ctx->evbuf_bytes < bytes) {
-    dev_free(ctx->evbuf);
     ctx->evbuf_bytes = 0;
-    if (dev_alloc(ctx, &ctx->evbuf, bytes) != KS_OK) return KS_ENOMEM;
+    if (dev_alloc(ctx, ctx->evbuf, bytes) != KS_OK) return KS_ENOMEM;
     ctx->evbuf_bytes = bytes;
   }
-  void* buf = ctx->evbuf;
+  void* buf = ctx->evbuf.get();
   b.dr = (uint32_t*)buf;
   b.ds = (int64_t*)((char*)buf + ((size_t)n * 4 + 15) / 16 * 16);
   b.dt = b.ds + (size_t)n * KS_NUM_SCORE_PLUGINS;
@@ -3989,13 +4006,13 @@ static int ev_buffers(ks_ctx* ctx, EvBuf& b) {
 static TopoKArgs topo_args(ks_ctx* ctx, PodStage& st, const int32_t* cursor, const EvBuf& eb) {
   TopoKArgs a{};
   a.t = dev_topo(ctx);
-  a.labels = ctx->d.labels;
+  a.labels = ctx->nodes.d.labels;
   a.stat = st.stat;
-  a.trec = st.topo;
-  a.terms = st.topo_terms;
+  a.trec = st.topo.get();
+  a.terms = st.topo_terms.get();
   a.cursor = cursor;
-  a.total_pods = cursor ? ctx->np : 1;
-  a.n = ctx->n;
+  a.total_pods = cursor ? ctx->staged.np : 1;
+  a.n = ctx->nodes.n;
   a.reasons = eb.dr;
   a.scores = eb.ds;
   a.total = eb.dt;
@@ -4004,8 +4021,8 @@ static TopoKArgs topo_args(ks_ctx* ctx, PodStage& st, const int32_t* cursor, con
   a.draw = eb.ddraw;
   a.traw = eb.dtraw;
   a.araw = eb.daraw;
-  a.sraw = ctx->topo_sraw;
-  a.iraw = ctx->topo_iraw;
+  a.sraw = ctx->topo.sraw;
+  a.iraw = ctx->topo.iraw;
   a.dev_on = ctx->kc.dev;
   a.taint_on = (ctx->kc.taint & 2) != 0;
   a.aff_on = (ctx->kc.aff & 2) != 0;
@@ -4016,35 +4033,35 @@ static TopoKArgs topo_args(ks_ctx* ctx, PodStage& st, const int32_t* cursor, con
   a.rsv_w = ctx->cfg.reservation.plugin_weight;
   a.spread_w = ctx->cfg.topology.spread_weight;
   a.ipa_w = ctx->cfg.topology.affinity_weight;
-  a.scr = ctx->topo_scr;
+  a.scr = ctx->topo.scr;
   if (cursor) {
-    a.cand_chunk = ctx->topo_cchunk;
-    a.cand_t = ctx->topo_ct;
-    a.cand_count = ctx->topo_ccount;
-    a.cand_bound = ctx->topo_cbound;
-    a.cand_top = ctx->topo_ctop;
-    a.cand_second = ctx->topo_csecond;
+    a.cand_chunk = ctx->topo.cchunk;
+    a.cand_t = ctx->topo.ct;
+    a.cand_count = ctx->topo.ccount;
+    a.cand_bound = ctx->topo.cbound;
+    a.cand_top = ctx->topo.ctop;
+    a.cand_second = ctx->topo.csecond;
   }
   return a;
 }
 
 // cpuset_kernel at the context's NUMA width
 static void cpuset_launch(ks_ctx* ctx, const PodRec* recs) {
-  const dim3 grid((unsigned)((ctx->n + 255) / 256));
+  const dim3 grid((unsigned)((ctx->nodes.n + 255) / 256));
   const int32_t most = (int32_t)(ctx->cfg.numa.numa_scoring_strategy == KS_MOST_ALLOCATED);
-  if (ctx->numa_w == kNumaWide)
-    hipLaunchKernelGGL(cpuset_kernel<kNumaWide>, grid, dim3(256), 0, ctx->stream, ctx->cpu, (const int2*)ctx->cpuset_list,
+  if (ctx->numa.w == kNumaWide)
+    hipLaunchKernelGGL(cpuset_kernel<kNumaWide>, grid, dim3(256), 0, ctx->stream, ctx->cpus.cpu, (const int2*)ctx->cpuset_list.get(),
                        (const int32_t*)ctx->cpuset_n, (const uint32_t*)ctx->cpuset_split, recs, ctx->cpuset_out,
-                       (const uint32_t*)ctx->d.numa_flags, ctx->d.cpu_cores, most, numa_words(ctx), ctx->nv.npad, ctx->n);
+                       (const uint32_t*)ctx->nodes.d.numa_flags, ctx->nodes.d.cpu_cores, most, numa_words(ctx), ctx->numa.nv.npad, ctx->nodes.n);
   else
-    hipLaunchKernelGGL(cpuset_kernel<kNumaDev>, grid, dim3(256), 0, ctx->stream, ctx->cpu, (const int2*)ctx->cpuset_list,
+    hipLaunchKernelGGL(cpuset_kernel<kNumaDev>, grid, dim3(256), 0, ctx->stream, ctx->cpus.cpu, (const int2*)ctx->cpuset_list.get(),
                        (const int32_t*)ctx->cpuset_n, (const uint32_t*)ctx->cpuset_split, recs, ctx->cpuset_out,
-                       (const uint32_t*)ctx->d.numa_flags, ctx->d.cpu_cores, most, numa_words(ctx), ctx->nv.npad, ctx->n);
+                       (const uint32_t*)ctx->nodes.d.numa_flags, ctx->nodes.d.cpu_cores, most, numa_words(ctx), ctx->numa.nv.npad, ctx->nodes.n);
 }
 
 // the pass's CPU ids (cores mode): exact per-node core counts for the next sweep (Cfg.cores)
 static int cores_pass_refresh(ks_ctx* ctx) {
-  if (!(ctx->kc.cores && ctx->cpu_loaded)) return KS_OK;
+  if (!(ctx->kc.cores && ctx->cpus.loaded)) return KS_OK;
   cpuset_launch(ctx, (const PodRec*)ctx->st.recs);
   HIPCHK(ctx, hipMemsetAsync(ctx->cpuset_n, 0, 4, ctx->stream));
   return KS_OK;
@@ -4056,51 +4073,51 @@ static int cores_pass_refresh(ks_ctx* ctx) {
 static int topo_step(ks_ctx* ctx) {
   EvBuf eb;
   if (ev_buffers(ctx, eb) != KS_OK) return KS_ENOMEM;
-  const int64_t n = ctx->n;
-  TopoKArgs ta = topo_args(ctx, ctx->st, ctx->cursor, eb);
+  const int64_t n = ctx->nodes.n;
+  TopoKArgs ta = topo_args(ctx, ctx->st, ctx->cursor.get(), eb);
   ta.scores = nullptr;  // (the batch step returns no per-plugin score matrix)
   HIPCHK(ctx, launch_topo_sums(ctx->stream, ta));
-  HIPCHK(ctx, launch_eval_debug(ctx->nsc, (int)((n + 255) / 256), ctx->stream, ctx->d, ctx->drv, ctx->ddv, ctx->dnv,
+  HIPCHK(ctx, launch_eval_debug(ctx->nodes.nsc, (int)((n + 255) / 256), ctx->stream, ctx->nodes.d, ctx->drv.get(), ctx->ddv.get(), ctx->dnv.get(),
                                 ctx->kc, ctx->st.recs, n, eb.dr, nullptr, eb.dt, eb.draw, eb.dhi, eb.ddraw, ctx->st.stat,
-                                eb.dtraw, eb.daraw, &ta, kernel_feat(ctx), ctx->numa_w));
+                                eb.dtraw, eb.daraw, &ta, kernel_feat(ctx), ctx->numa.w));
   HIPCHK(ctx, launch_topo_pts(ctx->stream, ta));
   const int feat = kernel_feat(ctx);
-  if ((feat == 0 || feat == 4) && !ctx->kc.dev && !ctx->kc.rsv && !ctx->kc.numa && !ctx->cpu_loaded) {
+  if ((feat == 0 || feat == 4) && !ctx->kc.dev && !ctx->kc.rsv && !ctx->kc.numa && !ctx->cpus.loaded) {
     // Reserve = NodeInfo.AddPod + the LoadAware assign cache + ElasticQuota: the lean commit, by the normalize
     // kernel's last workgroup
     TopoCommitArgs tc;
-    tc.d = ctx->d;
-    tc.q = ctx->q;
+    tc.d = ctx->nodes.d;
+    tc.q = ctx->quota.q;
     tc.pq = ctx->st.pq;
     tc.pods = ctx->st.recs;
     tc.pstat = ctx->st.stat;
-    tc.trec = ctx->st.topo;
-    tc.props = ctx->st.topo_props;
-    tc.cursor = ctx->cursor;
-    tc.total_pods = ctx->np;
+    tc.trec = ctx->st.topo.get();
+    tc.props = ctx->st.topo_props.get();
+    tc.cursor = ctx->cursor.get();
+    tc.total_pods = ctx->staged.np;
     tc.quota_enable = ctx->kc.quota_enable;
     tc.quota_parent = ctx->kc.quota_parent;
     tc.ports = ctx->kc.ports;
     tc.results = ctx->st.results;
-    tc.counters = ctx->counters;
-    tc.topo_count = ctx->topo_count;
-    tc.topo_npad = ctx->npad;
-    tc.scr = ctx->topo_scr;
+    tc.counters = ctx->counters.get();
+    tc.topo_count = ctx->topo.count;
+    tc.topo_npad = ctx->nodes.npad;
+    tc.scr = ctx->topo.scr;
     HIPCHK(ctx, launch_topo_norm(ctx->stream, ta, &tc));
     return KS_OK;
   }
   HIPCHK(ctx, launch_topo_norm(ctx->stream, ta));
-  CommitArgs ca = commit_args(ctx, ctx->st, ctx->np, 1);
+  CommitArgs ca = commit_args(ctx, ctx->st, ctx->staged.np, 1);
   ca.topo = 2;
-  ca.cand_chunk = ctx->topo_cchunk;
-  ca.cand_t = ctx->topo_ct;
-  ca.cand_count = ctx->topo_ccount;
-  ca.cand_bound = ctx->topo_cbound;
-  ca.cand_top = ctx->topo_ctop;
-  ca.cand_second = ctx->topo_csecond;
+  ca.cand_chunk = ctx->topo.cchunk;
+  ca.cand_t = ctx->topo.ct;
+  ca.cand_count = ctx->topo.ccount;
+  ca.cand_bound = ctx->topo.cbound;
+  ca.cand_top = ctx->topo.ctop;
+  ca.cand_second = ctx->topo.csecond;
   // one pod: the quota rows are read from HBM (copying the table into LDS would cost more than the pod's reads)
   const CommitPlan& plan = ctx->plan;
-  HIPCHK(ctx, pass_launcher(plan.feat, ctx->nsc, plan.wide).commit(false, plan.smem_no_qcache, ctx->stream, ca));
+  HIPCHK(ctx, pass_launcher(plan.feat, ctx->nodes.nsc, plan.wide).commit(false, plan.smem_no_qcache, ctx->stream, ca));
   return cores_pass_refresh(ctx);
 }
 
@@ -4120,36 +4137,36 @@ static int launch_pass(ks_ctx* ctx, int32_t ppw, int sweep_blocks, const PipeSha
   // the re-sweep (and patch): patched passes run it on the commit stream, between commit k-1 and commit k
   hipStream_t fs = patch ? ctx->cstream : ss;
   const CandSet cset = cand_set(ctx, patch ? (int)(k & 1) : 0);
-  uint2* sout = ctx->sweep_out + (patch ? (size_t)(k & 1) * kMaxBatch * ctx->nchunks : 0);
-  int32_t* base = pipe ? ctx->pipe + (k & 1) : ctx->cursor;  // the first pod this pass sweeps
-  int32_t* carry = ctx->pipe + 4;
+  uint2* sout = ctx->nodes.sweep_out.get() + (patch ? (size_t)(k & 1) * kMaxBatch * ctx->nodes.nchunks : 0);
+  int32_t* base = pipe ? ctx->pipe.get() + (k & 1) : ctx->cursor.get();  // the first pod this pass sweeps
+  int32_t* carry = ctx->pipe.get() + 4;
   auto rec = [&](int kind, hipStream_t s) {
     if (!evs) return;
     hipEvent_t e = take_event(ctx, *evn);
     (void)hipEventRecord(e, s);
     evs->push_back({kind, (*evn)++});
   };
-  auto shard_lo = [&](int32_t sh) { return ctx->nchunks * sh / S; };
+  auto shard_lo = [&](int32_t sh) { return ctx->nodes.nchunks * sh / S; };
   if (ctx->cfg.topology.enable && ctx->st.ndyn > 0 && !pipe) {
     // the topology pods at the cursor are scheduled alone first, up to topo_k of them in a row (timed with the
     // commits); a step whose cursor pod is not one costs its launches only
     rec(2, ctx->stream);
-    for (int32_t t = 0; t < ctx->topo_k; ++t)
+    for (int32_t t = 0; t < ctx->topo.k; ++t)
       if (int rc = topo_step(ctx); rc != KS_OK) return rc;
     rec(2, ctx->stream);
   }
   SweepArgs sa;
-  sa.dn = ctx->dnodes;
-  sa.rv = ctx->drv;
+  sa.dn = ctx->dnodes.get();
+  sa.rv = ctx->drv.get();
   sa.c = ctx->kc;
   sa.pods = ctx->st.recs;
   sa.cursor = base;
   sa.out = sout;
-  sa.n = ctx->n;
-  sa.nchunks = ctx->nchunks;
+  sa.n = ctx->nodes.n;
+  sa.nchunks = ctx->nodes.nchunks;
   sa.c0 = shard_lo(ctx->rank * ctx->vshards);
   sa.c1 = shard_lo((ctx->rank + 1) * ctx->vshards);
-  sa.total_pods = ctx->np;
+  sa.total_pods = ctx->staged.np;
   sa.batch = ctx->batch;
   sa.ppw = ppw;
   sa.fix = nullptr;
@@ -4161,17 +4178,17 @@ static int launch_pass(ks_ctx* ctx, int32_t ppw, int sweep_blocks, const PipeSha
   sa.list_top = nullptr;
   sa.list_k = 0;
   const int feat = kernel_feat(ctx);
-  sa.dv = ctx->ddv;
-  sa.nv = ctx->dnv;
-  sa.dev_M = ctx->dev_M;
-  sa.dcache = (ctx->kc.dev && !ctx->kc.rsv && !ctx->kc.stat && ctx->dcache_words >= (int64_t)kMaxBatch * ctx->npad)
-                  ? ctx->dcache : nullptr;
+  sa.dv = ctx->ddv.get();
+  sa.nv = ctx->dnv.get();
+  sa.dev_M = ctx->dev_M.get();
+  sa.dcache = (ctx->kc.dev && !ctx->kc.rsv && !ctx->kc.stat && ctx->dcache_words >= (int64_t)kMaxBatch * ctx->nodes.npad)
+                  ? ctx->dcache.get() : nullptr;
   sa.pstat = ctx->st.stat;
-  sa.dstride = ctx->npad;
+  sa.dstride = ctx->nodes.npad;
   sa.phase = 1;
   // One sweep launch per virtual shard (a rank's virtual shards are swept as separate chunk ranges, so the
   // c0 > 0 decode of every non-first shard runs on one GPU too); timed together as one launch.
-  const PassLaunch pl = pass_launcher(feat, NSC, ctx->numa_w == kNumaWide);
+  const PassLaunch pl = pass_launcher(feat, NSC, ctx->numa.w == kNumaWide);
   hipError_t le = hipSuccess;
   auto sweep = [&](int blocks, hipStream_t st) {
     for (int32_t v = 0; v < ctx->vshards && le == hipSuccess; ++v) {
@@ -4186,13 +4203,13 @@ static int launch_pass(ks_ctx* ctx, int32_t ppw, int sweep_blocks, const PipeSha
   if (feat & 4) {
     // DeviceShare: phase 0 reduces the per-pod normalization max, (RCCL max over the ranks), phase 1 keys;
     // each launch is timed on its own (the roofline is per sweep launch)
-    HIPCHK(ctx, hipMemsetAsync(ctx->dev_M, 0, kNormRows * kMaxBatch * 8, ss));
+    HIPCHK(ctx, hipMemsetAsync(ctx->dev_M.get(), 0, kNormRows * kMaxBatch * 8, ss));
     sa.phase = 0;
     rec(0, ss);
     sweep(sweep_blocks, ss);
     rec(0, ss);
     if (ctx->comm || ctx->loop)
-      if (int rc = exchange_allreduce_max(ctx, ctx->dev_M, kNormRows * kMaxBatch, ss); rc != KS_OK) return rc;
+      if (int rc = exchange_allreduce_max(ctx, ctx->dev_M.get(), kNormRows * kMaxBatch, ss); rc != KS_OK) return rc;
     sa.phase = 1;
     rec(0, ss);
     sweep(sweep_blocks, ss);
@@ -4214,7 +4231,7 @@ static int launch_pass(ks_ctx* ctx, int32_t ppw, int sweep_blocks, const PipeSha
       HIPCHK(ctx, hipStreamWaitEvent(fs, ctx->pev_com[(k - 1) % kPipeEvents], 0));
     }
     sa.fix = carry;
-    sa.fix_cursor = ctx->cursor;
+    sa.fix_cursor = ctx->cursor.get();
     sa.ppw = pipe->fix_ppw;
     rec(3, fs);
     if (patch) {
@@ -4223,7 +4240,7 @@ static int launch_pass(ks_ctx* ctx, int32_t ppw, int sweep_blocks, const PipeSha
       sa.list_chunk = cset.chunk;
       sa.list_count = cset.count;
       sa.list_bound = cset.bound;
-      sa.list_top = ctx->pipe_top + (size_t)(k & 1) * kMaxBatch;
+      sa.list_top = ctx->pipe_top.get() + (size_t)(k & 1) * kMaxBatch;
       sa.list_k = ctx->k;
       le = pl.sweep(pipe->list_blocks, fs, sa);  // once: the (merged) lists span every shard's chunks
     } else {
@@ -4238,11 +4255,11 @@ static int launch_pass(ks_ctx* ctx, int32_t ppw, int sweep_blocks, const PipeSha
   SelectArgs se;
   se.in = sout;
   se.cursor = base;
-  se.nchunks = ctx->nchunks;
-  se.total_pods = ctx->np;
+  se.nchunks = ctx->nodes.nchunks;
+  se.total_pods = ctx->staged.np;
   se.batch = ctx->batch;
   se.k = ctx->k;
-  se.real_cursor = ctx->cursor;
+  se.real_cursor = ctx->cursor.get();
   se.pods = ctx->st.recs;
   const CandSlot L = cand_slot_layout(ctx->k);
   rec(1, ss);
@@ -4250,7 +4267,7 @@ static int launch_pass(ks_ctx* ctx, int32_t ppw, int sweep_blocks, const PipeSha
     const int32_t sh = ctx->rank * ctx->vshards + v;
     se.c0 = shard_lo(sh);
     se.c1 = shard_lo(sh + 1);
-    se.next_base = (pipe && !patch && v == 0) ? ctx->pipe + ((k + 1) & 1) : nullptr;
+    se.next_base = (pipe && !patch && v == 0) ? ctx->pipe.get() + ((k + 1) & 1) : nullptr;
     if (S == 1) {
       se.cand_chunk = cset.chunk;
       se.cand_t = cset.t;
@@ -4260,7 +4277,7 @@ static int launch_pass(ks_ctx* ctx, int32_t ppw, int sweep_blocks, const PipeSha
       se.cand_count = cset.count;
       se.cand_total = cset.total;
     } else {
-      unsigned char* b = ctx->gather + (size_t)sh * L.bytes;
+      unsigned char* b = ctx->gather.get() + (size_t)sh * L.bytes;
       se.cand_chunk = (uint32_t*)(b + L.chunk);
       se.cand_t = (uint2*)(b + L.t);
       se.cand_bound = cset.bound;  // scratch: recomputed by the merge
@@ -4275,7 +4292,7 @@ static int launch_pass(ks_ctx* ctx, int32_t ppw, int sweep_blocks, const PipeSha
     if (ctx->comm || ctx->loop)  // every rank's candidate slots to every rank (one RCCL allgather per pass over xGMI)
       if (int rc = exchange_allgather(ctx, (size_t)ctx->vshards * L.bytes, ss); rc != KS_OK) return rc;
     MergeArgs ma;
-    ma.gather = ctx->gather;
+    ma.gather = ctx->gather.get();
     ma.cursor = base;
     ma.cand_chunk = cset.chunk;
     ma.cand_t = cset.t;
@@ -4284,7 +4301,7 @@ static int launch_pass(ks_ctx* ctx, int32_t ppw, int sweep_blocks, const PipeSha
     ma.cand_second = cset.second;
     ma.cand_count = cset.count;
     ma.nslots = S;
-    ma.total_pods = ctx->np;
+    ma.total_pods = ctx->staged.np;
     ma.batch = ctx->batch;
     ma.k = ctx->k;
     hipLaunchKernelGGL(merge_kernel, dim3(ctx->batch), dim3(64), 0, ss, ma);
@@ -4300,7 +4317,7 @@ static int launch_pass(ks_ctx* ctx, int32_t ppw, int sweep_blocks, const PipeSha
     HIPCHK(ctx, hipStreamWaitEvent(cs, ctx->pev_sel[k % kPipeEvents], 0));
   }
   const CommitPlan& plan = ctx->plan;
-  CommitArgs ca = commit_args(ctx, ctx->st, ctx->np, ctx->batch);
+  CommitArgs ca = commit_args(ctx, ctx->st, ctx->staged.np, ctx->batch);
   if (pipe) {
     ca.pipe_base = base;
     ca.carry = carry;
@@ -4312,17 +4329,17 @@ static int launch_pass(ks_ctx* ctx, int32_t ppw, int sweep_blocks, const PipeSha
   ca.cand_second = cset.second;
   ca.cand_count = cset.count;
   if (patch) {
-    ca.pipe_follow = ctx->pipe + ((k + 1) & 1);
+    ca.pipe_follow = ctx->pipe.get() + ((k + 1) & 1);
     ca.pipe_after = base;
-    ca.cand_top = (const uint64_t*)(ctx->pipe_top + (size_t)(k & 1) * kMaxBatch);  // rebuilt by the list re-evaluation
-    ca.top_reset = ctx->pipe_top + (size_t)(k & 1) * kMaxBatch;
+    ca.cand_top = (const uint64_t*)(ctx->pipe_top.get() + (size_t)(k & 1) * kMaxBatch);  // rebuilt by the list re-evaluation
+    ca.top_reset = ctx->pipe_top.get() + (size_t)(k & 1) * kMaxBatch;
   }
-  if (!plan.mono && !pipe && pl.reserve_pre && plan.pre_reserve) ca.pre_rsv = ctx->pre_rsv;
+  if (!plan.mono && !pipe && pl.reserve_pre && plan.pre_reserve) ca.pre_rsv = ctx->pre_rsv.get();
   rec(2, cs);
   if (ca.pre_rsv) HIPCHK(ctx, pl.reserve_pre(ctx->batch, cs, ca));  // (timed with the commit)
   // (the dedicated fq kernel does not run the patched pipeline's passes, ks_plan.h)
   if (plan.mono) HIPCHK(ctx, pl.commit_mono(plan.qcache, plan.mono_smem, cs, ca));
-  else if (plan.fq && !patch) HIPCHK(ctx, fq_launcher(ctx->nsc).commit(plan.fq_keys, plan.fq_smem, cs, ca));
+  else if (plan.fq && !patch) HIPCHK(ctx, fq_launcher(ctx->nodes.nsc).commit(plan.fq_keys, plan.fq_smem, cs, ca));
   else HIPCHK(ctx, pl.commit(plan.qcache, plan.smem, cs, ca));
   rec(2, cs);
   if (pipe) HIPCHK(ctx, hipEventRecord(ctx->pev_com[k % kPipeEvents], cs));
@@ -4332,51 +4349,43 @@ static int launch_pass(ks_ctx* ctx, int32_t ppw, int sweep_blocks, const PipeSha
 }
 
 static int schedule_staged_impl(ks_ctx* ctx) {
-  if (!ctx->node_blob) KS_FAIL(ctx, KS_ESTATE, "schedule before ks_load_nodes");
+  if (!ctx->nodes.blob.get()) KS_FAIL(ctx, KS_ESTATE, "schedule before ks_load_nodes");
   KS_NOM_REFUSE(ctx, "ks_schedule_staged");
-  if (ctx->staged_stale)
+  if (ctx->staged.stale)
     KS_FAIL(ctx, KS_ESTATE, "ks_schedule_staged: the staged batch predates a table reload; call ks_stage_pods again");
   HIPCHK(ctx, hipSetDevice(ctx->device));
-  bind_mode(ctx, ctx->staged_bind_required);
-  ctx->cpusets_clobbered = false;
+  bind_mode(ctx, ctx->staged.bind_required);
+  ctx->staged.cpusets_clobbered = false;
   ctx->stats = ks_stats{};
-  const int32_t np = ctx->np;
+  const int32_t np = ctx->staged.np;
   if (np == 0) return KS_OK;
   {
     if (int rc = commit_attr_set(ctx); rc != KS_OK) return rc;
     hipError_t e = hipSuccess;
-    const size_t sel_smem = select_smem(ctx->nchunks);
-    if (sel_smem > kLdsBytes) KS_FAIL(ctx, KS_EUNSUPPORTED, "too many nodes for the select kernel's LDS (%lld nodes)", (long long)ctx->n);
+    const size_t sel_smem = select_smem(ctx->nodes.nchunks);
+    if (sel_smem > kLdsBytes) KS_FAIL(ctx, KS_EUNSUPPORTED, "too many nodes for the select kernel's LDS (%lld nodes)", (long long)ctx->nodes.n);
     e = hipFuncSetAttribute((const void*)select_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sel_smem);
     if (e != hipSuccess) KS_FAIL(ctx, KS_EHIP, "hipFuncSetAttribute(select LDS %zu): %s", sel_smem, hipGetErrorString(e));
-    if (ctx->kc.dev && !ctx->kc.rsv && !ctx->kc.stat && ctx->dcache_words < (int64_t)kMaxBatch * ctx->npad) {
-      void* q = ctx->dcache;
-      dev_free(q);
-      ctx->dcache = nullptr;
+    if (ctx->kc.dev && !ctx->kc.rsv && !ctx->kc.stat && ctx->dcache_words < (int64_t)kMaxBatch * ctx->nodes.npad) {
       ctx->dcache_words = 0;
-      if (dev_alloc(ctx, &q, (size_t)kMaxBatch * ctx->npad * 8) != KS_OK) return KS_ENOMEM;
-      ctx->dcache = (unsigned long long*)q;
-      ctx->dcache_words = (int64_t)kMaxBatch * ctx->npad;
+      if (dev_alloc(ctx, ctx->dcache, (size_t)kMaxBatch * ctx->nodes.npad * 8) != KS_OK) return KS_ENOMEM;
+      ctx->dcache_words = (int64_t)kMaxBatch * ctx->nodes.npad;
     }
     const size_t gb = (size_t)ctx->nranks * ctx->vshards * cand_slot_layout(ctx->k).bytes;
     if (ctx->nranks * ctx->vshards > 1 && ctx->gather_bytes < gb) {
-      void* g = ctx->gather;
-      dev_free(g);
-      ctx->gather = nullptr;
-      if (dev_alloc(ctx, &g, gb) != KS_OK) return KS_ENOMEM;
-      HIPCHK(ctx, hipMemsetAsync(g, 0, gb, ctx->stream));
-      ctx->gather = (unsigned char*)g;
+      if (dev_alloc(ctx, ctx->gather, gb) != KS_OK) return KS_ENOMEM;
+      HIPCHK(ctx, hipMemsetAsync(ctx->gather.get(), 0, gb, ctx->stream));
       ctx->gather_bytes = gb;
     }
   }
   // topology steps per regular pass: about the queue's topology pods per other pod (a regular pass that meets a
   // topology pod at the cursor costs its launches for nothing), 1..8
-  ctx->topo_k = 1;
+  ctx->topo.k = 1;
   if (ctx->cfg.topology.enable && ctx->st.ndyn > 0)
-    ctx->topo_k = (int32_t)std::min<int64_t>(8, 1 + (int64_t)ctx->st.ndyn / std::max<int64_t>(1, (int64_t)np - ctx->st.ndyn));
+    ctx->topo.k = (int32_t)std::min<int64_t>(8, 1 + (int64_t)ctx->st.ndyn / std::max<int64_t>(1, (int64_t)np - ctx->st.ndyn));
   // pods per wave: aim for >= ~4096 waves per sweep
   const int64_t S = (int64_t)ctx->nranks * ctx->vshards;
-  const int64_t local_chunks = ctx->nchunks * (ctx->rank + 1) * ctx->vshards / S - ctx->nchunks * ctx->rank * ctx->vshards / S;
+  const int64_t local_chunks = ctx->nodes.nchunks * (ctx->rank + 1) * ctx->vshards / S - ctx->nodes.nchunks * ctx->rank * ctx->vshards / S;
   static const int64_t env_waves = env_i64("KS_SWEEP_WAVES", 4096, 64, (int64_t)1 << 24);
   static const int64_t env_ppw = env_i64("KS_SWEEP_PPW", 0, 1, kMaxBatch);
   static const int64_t env_cap = env_i64("KS_SWEEP_BLOCK_CAP", 2048, 8, 65535 * 8);
@@ -4388,13 +4397,13 @@ static int schedule_staged_impl(ks_ctx* ctx) {
   const int sweep_blocks = (int)((std::max<int64_t>(1, std::min<int64_t>((nwork + 3) / 4, env_cap)) + 7) & ~7ll);  // % 8 == 0 (XCD swizzle)
   if (ensure_cpuset_bufs(ctx, np) != KS_OK) return KS_ENOMEM;
   hipEvent_t t0 = take_event(ctx, 0), t1 = take_event(ctx, 1);
-  if (ctx->cpuset_list) {
+  if (ctx->cpuset_list.get()) {
     HIPCHK(ctx, hipMemsetAsync(ctx->cpuset_n, 0, 4, ctx->stream));
     HIPCHK(ctx, hipMemsetAsync(ctx->cpuset_out, 0, (size_t)np * sizeof(CpuSet), ctx->stream));
-    HIPCHK(ctx, hipMemsetAsync(ctx->numa_alloc, 0, (size_t)np * 2 * ctx->numa_w * 8, ctx->stream));
+    HIPCHK(ctx, hipMemsetAsync(ctx->numa_alloc, 0, (size_t)np * 2 * ctx->numa.w * 8, ctx->stream));
   }
-  HIPCHK(ctx, hipMemsetAsync(ctx->cursor, 0, 4, ctx->stream));
-  HIPCHK(ctx, hipMemsetAsync(ctx->counters, 0, 256, ctx->stream));
+  HIPCHK(ctx, hipMemsetAsync(ctx->cursor.get(), 0, 4, ctx->stream));
+  HIPCHK(ctx, hipMemsetAsync(ctx->counters.get(), 0, 256, ctx->stream));
   // pipelined passes: pass 0 sweeps from pod 0, no commit has written rows yet
   PipeShape pshape{};
   const PipeShape* pipe = nullptr;
@@ -4409,11 +4418,11 @@ static int schedule_staged_impl(ks_ctx* ctx) {
     pshape.fix_blocks = (int)((std::max<int64_t>(1, (fwork + 3) / 4) + 7) & ~7ll);
     pshape.list_blocks = (int)((((int64_t)ctx->batch * ctx->k + 3) / 4 + 7) & ~7ll);
     pipe = &pshape;
-    HIPCHK(ctx, hipMemsetAsync(ctx->pipe, 0, kPipeWords * 4, ctx->stream));
+    HIPCHK(ctx, hipMemsetAsync(ctx->pipe.get(), 0, kPipeWords * 4, ctx->stream));
     // patched: pass 1's sweep starts before commit 0 has decided anything, behind pass 0's pods
     if (pshape.patch) {
-      HIPCHK(ctx, hipMemsetD32Async((hipDeviceptr_t)(ctx->pipe + 1), std::min(ctx->batch, np), 1, ctx->stream));
-      HIPCHK(ctx, hipMemsetAsync(ctx->pipe_top, 0, 2 * kMaxBatch * 8, ctx->stream));
+      HIPCHK(ctx, hipMemsetD32Async((hipDeviceptr_t)(ctx->pipe.get() + 1), std::min(ctx->batch, np), 1, ctx->stream));
+      HIPCHK(ctx, hipMemsetAsync(ctx->pipe_top.get(), 0, 2 * kMaxBatch * 8, ctx->stream));
     }
     ctx->pipe_k = 0;
   }
@@ -4432,7 +4441,7 @@ static int schedule_staged_impl(ks_ctx* ctx) {
   int32_t host_cursor = 0;
   int rounds = 0;
   auto one_pass = [&](std::vector<std::pair<int, size_t>>* ev) -> int {
-    switch (ctx->nsc) {
+    switch (ctx->nodes.nsc) {
       case 0: return launch_pass<0>(ctx, ppw, sweep_blocks, pipe, ev, &evn);
       case 2: return launch_pass<2>(ctx, ppw, sweep_blocks, pipe, ev, &evn);
       default: return launch_pass<4>(ctx, ppw, sweep_blocks, pipe, ev, &evn);
@@ -4478,7 +4487,7 @@ static int schedule_staged_impl(ks_ctx* ctx) {
       if (int rc = one_pass(ctx->cfg.profile ? &evs : nullptr); rc != KS_OK) return rc;
     }
     HIPCHK(ctx, hipGetLastError());
-    HIPCHK(ctx, hipMemcpyAsync(&host_cursor, ctx->cursor, 4, hipMemcpyDeviceToHost, cs));
+    HIPCHK(ctx, hipMemcpyAsync(&host_cursor, ctx->cursor.get(), 4, hipMemcpyDeviceToHost, cs));
     HIPCHK(ctx, hipStreamSynchronize(cs));
     if (++rounds > 1000000) KS_FAIL(ctx, KS_EHIP, "schedule made no progress");
   }
@@ -4487,14 +4496,14 @@ static int schedule_staged_impl(ks_ctx* ctx) {
     HIPCHK(ctx, hipEventRecord(ctx->pev_com[0], cs));
     HIPCHK(ctx, hipStreamWaitEvent(ctx->stream, ctx->pev_com[0], 0));
   }
-  if (ctx->cpu_loaded && ctx->n > 0) {
+  if (ctx->cpus.loaded && ctx->nodes.n > 0) {
     // the CPU ids of the pass's cpu-bind Reserves (ks_cpuset.h), per node in placement order
     cpuset_launch(ctx, (const PodRec*)ctx->st.recs);
     HIPCHK(ctx, hipGetLastError());
   }
   HIPCHK(ctx, hipEventRecord(t1, ctx->stream));
   unsigned long long cnt[16] = {0};
-  HIPCHK(ctx, hipMemcpyAsync(cnt, ctx->counters, sizeof(cnt), hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(ctx, hipMemcpyAsync(cnt, ctx->counters.get(), sizeof(cnt), hipMemcpyDeviceToHost, ctx->stream));
   HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
   float ms = 0;
   (void)hipEventElapsedTime(&ms, t0, t1);
@@ -4526,7 +4535,7 @@ static int schedule_staged_impl(ks_ctx* ctx) {
     }
   }
   // algorithmic bytes of one full sweep launch: node columns read once per pod group + outputs
-  int64_t b_node = 8 * 15 + 4 * 3 + (int64_t)ctx->nsc * 16 + (ctx->kc.rsv ? 8 : 0) + (ctx->kc.numa ? 16 : 0) +
+  int64_t b_node = 8 * 15 + 4 * 3 + (int64_t)ctx->nodes.nsc * 16 + (ctx->kc.rsv ? 8 : 0) + (ctx->kc.numa ? 16 : 0) +
                    (ctx->kc.dev ? 4 + (kDevTW + kDevQW) * 8 : 0);
   const int64_t groups = (ctx->batch + ppw - 1) / ppw;
   ctx->stats.sweep_bytes = local_chunks * 64 * b_node * groups + (int64_t)ctx->batch * sizeof(PodRec) + local_chunks * 64 * 4;
@@ -4539,7 +4548,7 @@ int ks_schedule_staged(ks_ctx* ctx) {
 }
 
 int ks_fetch_results(ks_ctx* ctx, ks_result* out, int32_t p) {
-  if (!ctx || !out || p < 0 || p > ctx->np) return ctx ? (ctx->err = "ks_fetch_results: bad args", KS_EINVAL) : KS_EINVAL;
+  if (!ctx || !out || p < 0 || p > ctx->staged.np) return ctx ? (ctx->err = "ks_fetch_results: bad args", KS_EINVAL) : KS_EINVAL;
   if (p == 0) return KS_OK;
   HIPCHK(ctx, hipMemcpyAsync(out, ctx->st.results, (size_t)p * sizeof(ks_result), hipMemcpyDeviceToHost, ctx->stream));
   HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
@@ -4556,19 +4565,19 @@ int ks_schedule(ks_ctx* ctx, const ks_pod_cols* pods, int32_t p, ks_result* out)
 
 // ---- nominated pods (ks_nominated.h) ----
 
-// The device table from ctx->h_nom: CSR by node, a node's entries in descending priority (equal priorities in caller
+// The device table from ctx->nom.h_rows: CSR by node, a node's entries in descending priority (equal priorities in caller
 // order), the list of nodes with entries, and the overlay kernel's [n] output behind them.  No rows: no table.
 static int nom_install(ks_ctx* ctx) {
   HIPCHK(ctx, hipSetDevice(ctx->device));
   HIPCHK(ctx, hipStreamSynchronize(ctx->stream));  // (a kernel of the last call may still read the old table)
-  dev_free(ctx->nom_blob);
-  ctx->nomt = DevNominated{};
-  ctx->nom_fit = nullptr;
-  const size_t m = ctx->h_nom.size(), n = (size_t)ctx->n;
+  ctx->nom.blob.reset();
+  ctx->nom.nomt = DevNominated{};
+  ctx->nom.fit = nullptr;
+  const size_t m = ctx->nom.h_rows.size(), n = (size_t)ctx->nodes.n;
   if (m == 0) return KS_OK;
   std::vector<int32_t> order(m);
   for (size_t i = 0; i < m; ++i) order[i] = (int32_t)i;
-  const auto& rows = ctx->h_nom;
+  const auto& rows = ctx->nom.h_rows;
   std::stable_sort(order.begin(), order.end(), [&](int32_t x, int32_t y) {
     if (rows[x].node != rows[y].node) return rows[x].node < rows[y].node;
     return rows[x].prio > rows[y].prio;
@@ -4588,16 +4597,16 @@ static int nom_install(ks_ctx* ctx) {
   memcpy(h.data() + o_beg, beg.data(), (n + 1) * 8);
   memcpy(h.data() + o_nodes, nodes.data(), nodes.size() * 4);
   for (size_t pos = 0; pos < m; ++pos) {
-    const ks_ctx::NomRow& r = rows[(size_t)order[pos]];
+    const NomRow& r = rows[(size_t)order[pos]];
     memcpy(h.data() + o_prio + pos * 4, &r.prio, 4);
     memcpy(h.data() + o_id + pos * 8, &r.id, 8);
     for (int d = 0; d < kNomWords; ++d) memcpy(h.data() + o_req + ((size_t)d * m + pos) * 8, &r.req[d], 8);
   }
-  if (dev_alloc(ctx, &ctx->nom_blob, off) != KS_OK) return KS_ENOMEM;
-  HIPCHK(ctx, hipMemcpyAsync(ctx->nom_blob, h.data(), up, hipMemcpyHostToDevice, ctx->stream));
+  if (dev_alloc(ctx, ctx->nom.blob, off) != KS_OK) return KS_ENOMEM;
+  HIPCHK(ctx, hipMemcpyAsync(ctx->nom.blob.get(), h.data(), up, hipMemcpyHostToDevice, ctx->stream));
   HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-  unsigned char* b = (unsigned char*)ctx->nom_blob;
-  DevNominated& t = ctx->nomt;
+  unsigned char* b = (unsigned char*)ctx->nom.blob.get();
+  DevNominated& t = ctx->nom.nomt;
   t.beg = (const int64_t*)(b + o_beg);
   t.prio = (const int32_t*)(b + o_prio);
   t.id = (const int64_t*)(b + o_id);
@@ -4605,7 +4614,7 @@ static int nom_install(ks_ctx* ctx) {
   t.nodes = (const int32_t*)(b + o_nodes);
   t.m = (int64_t)m;
   t.nn = (int32_t)nodes.size();
-  ctx->nom_fit = (uint32_t*)(b + o_fit);
+  ctx->nom.fit = (uint32_t*)(b + o_fit);
   return KS_OK;
 }
 
@@ -4614,7 +4623,7 @@ int ks_load_nominated(ks_ctx* ctx, const ks_nominated_cols* cols, int64_t m, siz
   if (sizeof_cols != sizeof(ks_nominated_cols))
     KS_FAIL(ctx, KS_EINVAL, "ks_load_nominated: sizeof_cols %zu, this library's ks_nominated_cols has %zu bytes", sizeof_cols,
             sizeof(ks_nominated_cols));
-  if (!ctx->node_blob) KS_FAIL(ctx, KS_ESTATE, "ks_load_nominated before ks_load_nodes");
+  if (!ctx->nodes.blob.get()) KS_FAIL(ctx, KS_ESTATE, "ks_load_nominated before ks_load_nodes");
   if (m >= ((int64_t)1 << 31)) KS_FAIL(ctx, KS_EINVAL, "ks_load_nominated: too many pods");
   if (m > 0) {
     // the plugins whose Filters read the node's other pods beyond NodeInfo.Requested: adding a nominated pod would
@@ -4634,7 +4643,7 @@ int ks_load_nominated(ks_ctx* ctx, const ks_nominated_cols* cols, int64_t m, siz
     if (!cols->node || !cols->priority || !cols->id)
       KS_FAIL(ctx, KS_EINVAL, "ks_load_nominated: node, priority and id are required");
   }
-  std::vector<ks_ctx::NomRow> rows((size_t)m);
+  std::vector<NomRow> rows((size_t)m);
   if (m > 0) {
     const int64_t* reqc[kNomWords] = {cols->req_milli_cpu, cols->req_memory, cols->req_ephemeral, cols->req_scalar[0],
                                       cols->req_scalar[1], cols->req_scalar[2], cols->req_scalar[3]};
@@ -4649,84 +4658,56 @@ int ks_load_nominated(ks_ctx* ctx, const ks_nominated_cols* cols, int64_t m, siz
     }
     for (int64_t i = 0; i < m; ++i) {
       const int32_t nd = cols->node[i];
-      if (nd < 0 || nd >= ctx->n)
+      if (nd < 0 || nd >= ctx->nodes.n)
         KS_FAIL(ctx, KS_EINVAL, "ks_load_nominated: pod %lld nominated to node %d outside [0, %lld)", (long long)i, nd,
-                (long long)ctx->n);
-      ks_ctx::NomRow& r = rows[(size_t)i];
+                (long long)ctx->nodes.n);
+      NomRow& r = rows[(size_t)i];
       r.node = nd;
       r.prio = cols->priority[i];
       r.id = cols->id[i];
       for (int d = 0; d < kNomWords; ++d) r.req[d] = reqc[d] ? reqc[d][i] : 0;
     }
   }
-  ctx->h_nom.swap(rows);
+  ctx->nom.h_rows.swap(rows);
   return nom_install(ctx);
 }
 
 int ks_delete_nominated(ks_ctx* ctx, const int64_t* ids, int64_t m) {
   if (!ctx || m < 0 || (m > 0 && !ids)) return ctx ? (ctx->err = "ks_delete_nominated: bad args", KS_EINVAL) : KS_EINVAL;
-  if (!ctx->node_blob) KS_FAIL(ctx, KS_ESTATE, "ks_delete_nominated before ks_load_nodes");
+  if (!ctx->nodes.blob.get()) KS_FAIL(ctx, KS_ESTATE, "ks_delete_nominated before ks_load_nodes");
   std::vector<int64_t> gone(ids, ids + m);
   std::sort(gone.begin(), gone.end());
-  const size_t before = ctx->h_nom.size();
-  ctx->h_nom.erase(std::remove_if(ctx->h_nom.begin(), ctx->h_nom.end(),
-                                  [&](const ks_ctx::NomRow& r) { return std::binary_search(gone.begin(), gone.end(), r.id); }),
-                   ctx->h_nom.end());
-  if (ctx->h_nom.size() == before) return KS_OK;
+  const size_t before = ctx->nom.h_rows.size();
+  ctx->nom.h_rows.erase(std::remove_if(ctx->nom.h_rows.begin(), ctx->nom.h_rows.end(),
+                                  [&](const NomRow& r) { return std::binary_search(gone.begin(), gone.end(), r.id); }),
+                   ctx->nom.h_rows.end());
+  if (ctx->nom.h_rows.size() == before) return KS_OK;
   return nom_install(ctx);
 }
 
 int ks_checkpoint(ks_ctx* ctx) {
-  if (!ctx || !ctx->node_blob) return ctx ? (ctx->err = "ks_checkpoint before ks_load_nodes", KS_ESTATE) : KS_EINVAL;
-  if (!ctx->ckpt_blob && dev_alloc(ctx, &ctx->ckpt_blob, ctx->mut_bytes) != KS_OK) return KS_ENOMEM;
-  HIPCHK(ctx, hipMemcpyAsync(ctx->ckpt_blob, ctx->node_blob, ctx->mut_bytes, hipMemcpyDeviceToDevice, ctx->stream));
-  if (ctx->quota_blob) {
-    const size_t tb = (size_t)(ctx->q.q > 0 ? ctx->q.q : 1) * KS_QUOTA_DIMS * 8;
-    HIPCHK(ctx, hipMemcpyAsync(ctx->quota_used_ckpt, ctx->q.used, tb, hipMemcpyDeviceToDevice, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(ctx->quota_npused_ckpt, ctx->q.npused, tb, hipMemcpyDeviceToDevice, ctx->stream));
-  }
-  if (ctx->dev_blob)
-    HIPCHK(ctx, hipMemcpyAsync(ctx->dev_used_ckpt, ctx->dv.used, (size_t)kDevQW * ctx->dv.npad * 8, hipMemcpyDeviceToDevice, ctx->stream));
-  if (ctx->cpu_loaded)
-    HIPCHK(ctx, hipMemcpyAsync(ctx->cpu_ckpt, ctx->cpu.allocated, (size_t)3 * ctx->cpu.npad * sizeof(CpuSet), hipMemcpyDeviceToDevice, ctx->stream));
-  if (ctx->numa_blob)
-    HIPCHK(ctx, hipMemcpyAsync(ctx->numa_ckpt, ctx->nv.used, numa_mut_bytes((size_t)ctx->npad, ctx->numa_w), hipMemcpyDeviceToDevice, ctx->stream));
-  if (ctx->rsv_blob) {
-    HIPCHK(ctx, hipMemcpyAsync(ctx->rsv_allocd_ckpt, ctx->rv.allocd, (size_t)kRsvDims * ctx->rv.nr * 8, hipMemcpyDeviceToDevice, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(ctx->rsv_dald_ckpt, ctx->rv.dald, (size_t)kDevQW * ctx->rv.nr * 8, hipMemcpyDeviceToDevice, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(ctx->rsv_assigned_ckpt, ctx->rv.assigned, (size_t)ctx->rv.nr * 4, hipMemcpyDeviceToDevice, ctx->stream));
-  }
+  if (!ctx || !ctx->nodes.blob.get()) return ctx ? (ctx->err = "ks_checkpoint before ks_load_nodes", KS_ESTATE) : KS_EINVAL;
+  NodeTable& nd = ctx->nodes;
+  if (!nd.ckpt.get() && dev_alloc(ctx, nd.ckpt, nd.mut_bytes) != KS_OK) return KS_ENOMEM;
+  if (int rc = snap_copy(ctx, Snap{nd.blob.get(), nd.ckpt.get(), nd.mut_bytes}, false); rc != KS_OK) return rc;
+  for (const Snap& s : ctx->snaps())
+    if (int rc = snap_copy(ctx, s, false); rc != KS_OK) return rc;
   HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-  ctx->h_dev_assumed_ckpt = ctx->h_dev_assumed;
-  ctx->h_nom_ckpt = ctx->h_nom;
+  ctx->dev.checkpoint_host();
+  ctx->nom.checkpoint_host();
   return KS_OK;
 }
 
 int ks_restore(ks_ctx* ctx) {
-  if (!ctx || !ctx->ckpt_blob) return ctx ? (ctx->err = "ks_restore without ks_checkpoint", KS_ESTATE) : KS_EINVAL;
-  HIPCHK(ctx, hipMemcpyAsync(ctx->node_blob, ctx->ckpt_blob, ctx->mut_bytes, hipMemcpyDeviceToDevice, ctx->stream));
-  if (ctx->quota_blob) {
-    const size_t tb = (size_t)(ctx->q.q > 0 ? ctx->q.q : 1) * KS_QUOTA_DIMS * 8;
-    HIPCHK(ctx, hipMemcpyAsync(ctx->q.used, ctx->quota_used_ckpt, tb, hipMemcpyDeviceToDevice, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(ctx->q.npused, ctx->quota_npused_ckpt, tb, hipMemcpyDeviceToDevice, ctx->stream));
-  }
-  if (ctx->dev_blob)
-    HIPCHK(ctx, hipMemcpyAsync(ctx->dv.used, ctx->dev_used_ckpt, (size_t)kDevQW * ctx->dv.npad * 8, hipMemcpyDeviceToDevice, ctx->stream));
-  if (ctx->cpu_loaded)
-    HIPCHK(ctx, hipMemcpyAsync(ctx->cpu.allocated, ctx->cpu_ckpt, (size_t)3 * ctx->cpu.npad * sizeof(CpuSet), hipMemcpyDeviceToDevice, ctx->stream));
-  if (ctx->numa_blob)
-    HIPCHK(ctx, hipMemcpyAsync(ctx->nv.used, ctx->numa_ckpt, numa_mut_bytes((size_t)ctx->npad, ctx->numa_w), hipMemcpyDeviceToDevice, ctx->stream));
-  if (ctx->rsv_blob) {
-    HIPCHK(ctx, hipMemcpyAsync(ctx->rv.allocd, ctx->rsv_allocd_ckpt, (size_t)kRsvDims * ctx->rv.nr * 8, hipMemcpyDeviceToDevice, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(ctx->rv.dald, ctx->rsv_dald_ckpt, (size_t)kDevQW * ctx->rv.nr * 8, hipMemcpyDeviceToDevice, ctx->stream));
-    HIPCHK(ctx, hipMemcpyAsync(ctx->rv.assigned, ctx->rsv_assigned_ckpt, (size_t)ctx->rv.nr * 4, hipMemcpyDeviceToDevice, ctx->stream));
-  }
-  ctx->h_dev_assumed = ctx->h_dev_assumed_ckpt;
+  if (!ctx || !ctx->nodes.ckpt.get()) return ctx ? (ctx->err = "ks_restore without ks_checkpoint", KS_ESTATE) : KS_EINVAL;
+  NodeTable& nd = ctx->nodes;
+  if (int rc = snap_copy(ctx, Snap{nd.blob.get(), nd.ckpt.get(), nd.mut_bytes}, true); rc != KS_OK) return rc;
+  for (const Snap& s : ctx->snaps())
+    if (int rc = snap_copy(ctx, s, true); rc != KS_OK) return rc;
+  ctx->dev.restore_host();
   HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-  if (!ctx->h_nom.empty() || !ctx->h_nom_ckpt.empty()) {  // the nominated table as it was at the checkpoint
-    ctx->h_nom = ctx->h_nom_ckpt;
+  if (ctx->nom.restore_host())  // the nominated table as it was at the checkpoint
     if (int rc = nom_install(ctx); rc != KS_OK) return rc;
-  }
   return KS_OK;
 }
 
@@ -4748,12 +4729,11 @@ static int scatter_words(ks_ctx* ctx, void* dst, size_t elem, int64_t rs, int64_
   if (m == 0 || W == 0) return KS_OK;
   const size_t need = align16((size_t)m * 4) + (size_t)m * W * elem;
   if (ctx->dscratch_bytes < need) {
-    dev_free(ctx->dscratch);
     ctx->dscratch_bytes = 0;
-    if (dev_alloc(ctx, &ctx->dscratch, need) != KS_OK) return KS_ENOMEM;
+    if (dev_alloc(ctx, ctx->dscratch, need) != KS_OK) return KS_ENOMEM;
     ctx->dscratch_bytes = need;
   }
-  char* b = (char*)ctx->dscratch;
+  char* b = (char*)ctx->dscratch.get();
   HIPCHK(ctx, hipMemcpyAsync(b, idx.data(), (size_t)m * 4, hipMemcpyHostToDevice, ctx->stream));
   HIPCHK(ctx, hipMemcpyAsync(b + align16((size_t)m * 4), src, (size_t)m * W * elem, hipMemcpyHostToDevice, ctx->stream));
   const unsigned blocks = (unsigned)((m * W + 255) / 256);
@@ -4783,25 +4763,25 @@ static int check_idx(ks_ctx* ctx, const int32_t* idx, int64_t m, int64_t lim, co
 // deviceshare nodeDeviceCache.updateNodeDevice (device_cache.go:489-527): the device rows of m nodes
 int ks_update_devices(ks_ctx* ctx, const int32_t* idx, const ks_device_cols* rows, int64_t m) {
   if (!ctx || !rows || m < 0 || (m > 0 && !idx)) return ctx ? (ctx->err = "ks_update_devices: bad args", KS_EINVAL) : KS_EINVAL;
-  if (!ctx->dev_blob || !ctx->cfg.deviceshare.enable) KS_FAIL(ctx, KS_ESTATE, "ks_update_devices without a device table");
+  if (!ctx->dev.blob.get() || !ctx->cfg.deviceshare.enable) KS_FAIL(ctx, KS_ESTATE, "ks_update_devices without a device table");
   std::vector<int32_t> ix;
-  if (int rc = check_idx(ctx, idx, m, ctx->n, "ks_update_devices", ix); rc != KS_OK) return rc;
+  if (int rc = check_idx(ctx, idx, m, ctx->nodes.n, "ks_update_devices", ix); rc != KS_OK) return rc;
   for (int32_t i : ix)
-    if ((size_t)i < ctx->h_dev_assumed.size() && ctx->h_dev_assumed[(size_t)i] > 0)
+    if ((size_t)i < ctx->dev.h_assumed.size() && ctx->dev.h_assumed[(size_t)i] > 0)
       KS_FAIL(ctx, KS_ESTATE, "ks_update_devices: node %d holds %d assumed device pod(s); ks_unreserve them first (their "
-              "Unreserve subtracts the request derived from the current device totals)", i, ctx->h_dev_assumed[(size_t)i]);
+              "Unreserve subtracts the request derived from the current device totals)", i, ctx->dev.h_assumed[(size_t)i]);
   HIPCHK(ctx, hipSetDevice(ctx->device));
   std::vector<uint32_t> flags((size_t)m, 0);
   std::vector<int64_t> total((size_t)kDevTW * m, 0), used((size_t)kDevQW * m, 0);
   std::vector<uint16_t> ids((size_t)m, 0);
   if (int rc = dev_encode(ctx, rows, m, (size_t)m, flags.data(), total.data(), used.data(), ids.data()); rc != KS_OK) return rc;
-  const int64_t np = ctx->npad;
-  if (scatter_words(ctx, (void*)ctx->dv.flags, 4, 1, np, 1, ix, flags.data()) != KS_OK ||
-      scatter_words(ctx, (void*)ctx->dv.total, 8, 1, np, kDevTW, ix, total.data()) != KS_OK ||
-      scatter_words(ctx, (void*)ctx->dv.used, 8, 1, np, kDevQW, ix, used.data()) != KS_OK)
+  const int64_t np = ctx->nodes.npad;
+  if (scatter_words(ctx, (void*)ctx->dev.dv.flags, 4, 1, np, 1, ix, flags.data()) != KS_OK ||
+      scatter_words(ctx, (void*)ctx->dev.dv.total, 8, 1, np, kDevTW, ix, total.data()) != KS_OK ||
+      scatter_words(ctx, (void*)ctx->dev.dv.used, 8, 1, np, kDevQW, ix, used.data()) != KS_OK)
     return KS_EHIP;
-  for (int64_t i = 0; i < m; ++i) ctx->h_dev_ids[(size_t)ix[i]] = ids[(size_t)i];
-  ctx->dev_loaded = true;
+  for (int64_t i = 0; i < m; ++i) ctx->dev.h_ids[(size_t)ix[i]] = ids[(size_t)i];
+  ctx->dev.loaded = true;
   if (int rc = dev_apply_held(ctx); rc != KS_OK) return rc;
   return check_dev_numa(ctx);
 }
@@ -4811,36 +4791,36 @@ int ks_update_devices(ks_ctx* ctx, const int32_t* idx, const ks_device_cols* row
 int ks_update_cpu_state(ks_ctx* ctx, const int32_t* idx, const ks_cpu_state_cols* rows, int64_t m) {
   if (!ctx || !rows || m < 0 || (m > 0 && (!idx || !rows->topology || !rows->allocated)))
     return ctx ? (ctx->err = "ks_update_cpu_state: bad args", KS_EINVAL) : KS_EINVAL;
-  if (!ctx->cpu_loaded) KS_FAIL(ctx, KS_ESTATE, "ks_update_cpu_state before ks_load_cpu_state");
+  if (!ctx->cpus.loaded) KS_FAIL(ctx, KS_ESTATE, "ks_update_cpu_state before ks_load_cpu_state");
   std::vector<int32_t> ix;
-  if (int rc = check_idx(ctx, idx, m, ctx->n, "ks_update_cpu_state", ix); rc != KS_OK) return rc;
+  if (int rc = check_idx(ctx, idx, m, ctx->nodes.n, "ks_update_cpu_state", ix); rc != KS_OK) return rc;
   HIPCHK(ctx, hipSetDevice(ctx->device));
-  const int32_t ntopo = (int32_t)ctx->cpu_cpc.size();
+  const int32_t ntopo = (int32_t)ctx->cpus.cpc.size();
   std::vector<int32_t> tid((size_t)m), freec((size_t)m), ncpu((size_t)m);
   std::vector<CpuSet> sets((size_t)4 * m);
   for (int64_t i = 0; i < m; ++i) {
-    if (int rc = cpu_encode_row(ctx, rows, i, ix[(size_t)i], ntopo, ctx->h_topos, tid[(size_t)i], sets[(size_t)i],
+    if (int rc = cpu_encode_row(ctx, rows, i, ix[(size_t)i], ntopo, ctx->cpus.h_topos, tid[(size_t)i], sets[(size_t)i],
                                 sets[(size_t)m + i], sets[(size_t)2 * m + i], sets[(size_t)3 * m + i], freec[(size_t)i],
                                 ncpu[(size_t)i]);
         rc != KS_OK)
       return rc;
-    const int32_t k = (size_t)ix[(size_t)i] < ctx->h_numa_k.size() ? ctx->h_numa_k[(size_t)ix[(size_t)i]] : 0;
-    const int32_t nn = tid[(size_t)i] >= 0 ? (ctx->h_topo_dense[(size_t)tid[(size_t)i]] ? ctx->h_topos[(size_t)tid[(size_t)i]].nnodes : -1) : 0;
+    const int32_t k = (size_t)ix[(size_t)i] < ctx->numa.h_k.size() ? ctx->numa.h_k[(size_t)ix[(size_t)i]] : 0;
+    const int32_t nn = tid[(size_t)i] >= 0 ? (ctx->cpus.h_topo_dense[(size_t)tid[(size_t)i]] ? ctx->cpus.h_topos[(size_t)tid[(size_t)i]].nnodes : -1) : 0;
     if (k > 0 && nn != 0 && (nn < 0 || nn > k))
       KS_FAIL(ctx, KS_EUNSUPPORTED, "node %d: NUMA-policy node whose CPU topology NUMA ids are not 0..m-1 with m <= %d", ix[(size_t)i], k);
-    ctx->h_cpu_nn[(size_t)ix[(size_t)i]] = (int8_t)nn;
+    ctx->cpus.h_nn[(size_t)ix[(size_t)i]] = (int8_t)nn;
   }
   // CpuSet rows: 4 tables of [npad] CpuSet, kCpuW u64 words each, row-major
   std::vector<int64_t> words((size_t)kCpuW * m);
-  CpuSet* tables[4] = {ctx->cpu.allocated, ctx->cpu.excl_pcpu, ctx->cpu.excl_numa, const_cast<CpuSet*>(ctx->cpu.reserved)};
+  CpuSet* tables[4] = {ctx->cpus.cpu.allocated, ctx->cpus.cpu.excl_pcpu, ctx->cpus.cpu.excl_numa, const_cast<CpuSet*>(ctx->cpus.cpu.reserved)};
   for (int q = 0; q < 4; ++q) {
     for (int64_t i = 0; i < m; ++i)
       for (int w = 0; w < kCpuW; ++w) words[(size_t)w * m + i] = (int64_t)sets[(size_t)q * m + i].w[w];
     if (scatter_words(ctx, tables[q], 8, kCpuW, 1, kCpuW, ix, words.data()) != KS_OK) return KS_EHIP;
   }
-  if (scatter_words(ctx, (void*)ctx->cpu.topo_id, 4, 1, 0, 1, ix, tid.data()) != KS_OK ||
-      scatter_words(ctx, ctx->d.cpu_free, 4, 1, 0, 1, ix, freec.data()) != KS_OK ||
-      scatter_words(ctx, ctx->d.numa_cpus, 4, 1, 0, 1, ix, ncpu.data()) != KS_OK)
+  if (scatter_words(ctx, (void*)ctx->cpus.cpu.topo_id, 4, 1, 0, 1, ix, tid.data()) != KS_OK ||
+      scatter_words(ctx, ctx->nodes.d.cpu_free, 4, 1, 0, 1, ix, freec.data()) != KS_OK ||
+      scatter_words(ctx, ctx->nodes.d.numa_cpus, 4, 1, 0, 1, ix, ncpu.data()) != KS_OK)
     return KS_EHIP;
   if (upload_prep_nodes(ctx) != KS_OK || numa_refresh_free(ctx) != KS_OK || cores_refresh(ctx) != KS_OK)
     return KS_EHIP;  // cpuset millicores, offsets, per-NUMA free CPUs, core counts
@@ -4853,9 +4833,9 @@ int ks_update_cpu_state(ks_ctx* ctx, const int32_t* idx, const ks_cpu_state_cols
 // change is a ks_load_quotas)
 int ks_update_quotas(ks_ctx* ctx, const int32_t* idx, const ks_quota_cols* rows, int32_t m) {
   if (!ctx || !rows || m < 0 || (m > 0 && !idx)) return ctx ? (ctx->err = "ks_update_quotas: bad args", KS_EINVAL) : KS_EINVAL;
-  if (!ctx->quota_blob) KS_FAIL(ctx, KS_ESTATE, "ks_update_quotas before ks_load_quotas");
+  if (!ctx->quota.blob.get()) KS_FAIL(ctx, KS_ESTATE, "ks_update_quotas before ks_load_quotas");
   std::vector<int32_t> ix;
-  if (int rc = check_idx(ctx, idx, m, ctx->q.q, "ks_update_quotas", ix); rc != KS_OK) return rc;
+  if (int rc = check_idx(ctx, idx, m, ctx->quota.q.q, "ks_update_quotas", ix); rc != KS_OK) return rc;
   HIPCHK(ctx, hipSetDevice(ctx->device));
   std::vector<int32_t> lm((size_t)m), mm((size_t)m);
   std::vector<int64_t> t[4];
@@ -4867,9 +4847,9 @@ int ks_update_quotas(ks_ctx* ctx, const int32_t* idx, const ks_quota_cols* rows,
     for (int q = 0; q < 4; ++q)
       for (int d = 0; d < KS_QUOTA_DIMS; ++d) t[q][(size_t)d * m + i] = src[q][d] ? src[q][d][i] : 0;
   }
-  int64_t* dst[4] = {ctx->q.limit, ctx->q.used, ctx->q.min, ctx->q.npused};
-  if (scatter_words(ctx, ctx->q.limit_mask, 4, 1, 0, 1, ix, lm.data()) != KS_OK ||
-      scatter_words(ctx, ctx->q.min_mask, 4, 1, 0, 1, ix, mm.data()) != KS_OK)
+  int64_t* dst[4] = {ctx->quota.q.limit, ctx->quota.q.used, ctx->quota.q.min, ctx->quota.q.npused};
+  if (scatter_words(ctx, ctx->quota.q.limit_mask, 4, 1, 0, 1, ix, lm.data()) != KS_OK ||
+      scatter_words(ctx, ctx->quota.q.min_mask, 4, 1, 0, 1, ix, mm.data()) != KS_OK)
     return KS_EHIP;
   for (int q = 0; q < 4; ++q)
     if (scatter_words(ctx, dst[q], 8, KS_QUOTA_DIMS, 1, KS_QUOTA_DIMS, ix, t[q].data()) != KS_OK) return KS_EHIP;
@@ -4884,15 +4864,15 @@ int ks_update_reservation_usage(ks_ctx* ctx, const int32_t* rows, const int64_t*
                                 int32_t m) {
   if (!ctx || m < 0 || (m > 0 && (!rows || !allocated || !assigned)))
     return ctx ? (ctx->err = "ks_update_reservation_usage: bad args", KS_EINVAL) : KS_EINVAL;
-  if (!ctx->rsv_blob) KS_FAIL(ctx, KS_ESTATE, "ks_update_reservation_usage before ks_load_reservations");
+  if (!ctx->rsv.blob.get()) KS_FAIL(ctx, KS_ESTATE, "ks_update_reservation_usage before ks_load_reservations");
   std::vector<int32_t> ix;
-  if (int rc = check_idx(ctx, rows, m, (int64_t)ctx->h_rsv_gi.size(), "ks_update_reservation_usage", ix); rc != KS_OK) return rc;
+  if (int rc = check_idx(ctx, rows, m, (int64_t)ctx->rsv.h_gi.size(), "ks_update_reservation_usage", ix); rc != KS_OK) return rc;
   HIPCHK(ctx, hipSetDevice(ctx->device));
   std::vector<int32_t> gi((size_t)m), nodes;
   for (int32_t i = 0; i < m; ++i) {
-    gi[(size_t)i] = ctx->h_rsv_gi[(size_t)ix[(size_t)i]];
+    gi[(size_t)i] = ctx->rsv.h_gi[(size_t)ix[(size_t)i]];
     if (gi[(size_t)i] < 0) KS_FAIL(ctx, KS_EINVAL, "ks_update_reservation_usage: row %d was deleted", ix[(size_t)i]);
-    nodes.push_back(ctx->h_rsv_node[(size_t)gi[(size_t)i]]);
+    nodes.push_back(ctx->rsv.h_node[(size_t)gi[(size_t)i]]);
     for (int d = 0; d < kRsvDims; ++d)
       if (allocated[d] && (allocated[d][i] < 0 || allocated[d][i] >= ((int64_t)1 << 56)))
         KS_FAIL(ctx, KS_EINVAL, "reservation row %d: allocated out of range", ix[(size_t)i]);
@@ -4904,24 +4884,20 @@ int ks_update_reservation_usage(ks_ctx* ctx, const int32_t* rows, const int64_t*
   for (int d = 0; d < kRsvDims; ++d)
     for (int32_t i = 0; i < m; ++i) al[(size_t)d * m + i] = allocated[d] ? allocated[d][i] : 0;
   // the affected nodes' base restore out, the usage in, the restore (and the nodes' owner classes) back
-  int32_t* dn = nullptr;
-  {
-    void* p = nullptr;
-    if (dev_alloc(ctx, &p, nodes.size() * 4 + 16) != KS_OK) return KS_ENOMEM;
-    dn = (int32_t*)p;
-  }
+  DevPtr<int32_t> dn_owner;
+  if (dev_alloc(ctx, dn_owner, nodes.size() * 4 + 16) != KS_OK) return KS_ENOMEM;
+  int32_t* const dn = dn_owner.get();
   auto done = [&](int rc) {
-    void* p = dn;
     (void)hipStreamSynchronize(ctx->stream);
-    dev_free(p);
+    dn_owner.reset();
     return rc;
   };
   HIPCHK(ctx, hipMemcpyAsync(dn, nodes.data(), nodes.size() * 4, hipMemcpyHostToDevice, ctx->stream));
-  if (ctx->rsv_based && rsv_launch_base(ctx, dn, (int64_t)nodes.size(), -1, 0) != KS_OK) return done(KS_EHIP);
-  if (scatter_words(ctx, ctx->rv.allocd, 8, 1, ctx->rv.nr, kRsvDims, gi, al.data()) != KS_OK ||
-      scatter_words(ctx, ctx->rv.assigned, 4, 1, 0, 1, gi, assigned) != KS_OK)
+  if (ctx->rsv.based && rsv_launch_base(ctx, dn, (int64_t)nodes.size(), -1, 0) != KS_OK) return done(KS_EHIP);
+  if (scatter_words(ctx, ctx->rsv.rv.allocd, 8, 1, ctx->rsv.rv.nr, kRsvDims, gi, al.data()) != KS_OK ||
+      scatter_words(ctx, ctx->rsv.rv.assigned, 4, 1, 0, 1, gi, assigned) != KS_OK)
     return done(KS_EHIP);
-  if (ctx->rsv_based && rsv_launch_base(ctx, dn, (int64_t)nodes.size(), +1, 1) != KS_OK) return done(KS_EHIP);
+  if (ctx->rsv.based && rsv_launch_base(ctx, dn, (int64_t)nodes.size(), +1, 1) != KS_OK) return done(KS_EHIP);
   return done(KS_OK);
 }
 
@@ -4933,16 +4909,16 @@ int ks_update_reservation_usage(ks_ctx* ctx, const int32_t* rows, const int64_t*
 // it is feasible.  Without nom a loaded table refuses the call.
 static int eval_pod_launch(ks_ctx* ctx, const ks_pod_cols* pod, const char* who, EvBuf& eb,
                            const ks_nomination* nom = nullptr, int32_t only = -1) {
-  if (!ctx->node_blob) KS_FAIL(ctx, KS_ESTATE, "%s before ks_load_nodes", who);
+  if (!ctx->nodes.blob.get()) KS_FAIL(ctx, KS_ESTATE, "%s before ks_load_nodes", who);
   if (!nom) KS_NOM_REFUSE(ctx, who);
-  if (nom && (nom->nominated_node < -1 || nom->nominated_node >= ctx->n))
+  if (nom && (nom->nominated_node < -1 || nom->nominated_node >= ctx->nodes.n))
     KS_FAIL(ctx, KS_EINVAL, "%s: nominated node %d out of range", who, nom->nominated_node);
   if (int rc = validate_pods(ctx, pod, 1); rc != KS_OK) return rc;
-  bind_mode(ctx, ctx->val_bind_required);
+  bind_mode(ctx, ctx->staged.val_bind_required);
   HIPCHK(ctx, hipSetDevice(ctx->device));
   if (ensure_stage(ctx, ctx->est, 1) != KS_OK) return KS_ENOMEM;
   if (stage_cols(ctx, ctx->est, pod, 1) != KS_OK || prep_stage(ctx, ctx->est, 1) != KS_OK) return KS_EHIP;
-  const int64_t n = ctx->n;
+  const int64_t n = ctx->nodes.n;
   if (ev_buffers(ctx, eb) != KS_OK) return KS_ENOMEM;
   uint32_t* dr = eb.dr;
   int64_t* ds = eb.ds;
@@ -4951,36 +4927,36 @@ static int eval_pod_launch(ks_ctx* ctx, const ks_pod_cols* pod, const char* who,
   const int threads = 256;
   const int blocks = (int)((n + threads - 1) / threads);
   const uint32_t* nom_fit = nullptr;
-  if (nom && ctx->nomt.beg && blocks > 0) {
+  if (nom && ctx->nom.nomt.beg && blocks > 0) {
     // Fit with the nominated pods added, on the nodes that have any (a profile with topology terms has no table)
     const NomWho nw{nom->self_id, nom->priority};
-    const dim3 grid((unsigned)((ctx->nomt.nn + 3) / 4));
-    HIPCHK(ctx, hipMemsetAsync(ctx->nom_fit, 0, (size_t)n * 4, ctx->stream));
-    if (ctx->nsc == 0)
-      hipLaunchKernelGGL(nominated_overlay_kernel<0>, grid, dim3(256), 0, ctx->stream, ctx->nomt, ctx->d, ctx->kc,
-                         (const PodRec*)ctx->est.recs, nw, ctx->nom_fit);
-    else if (ctx->nsc == 2)
-      hipLaunchKernelGGL(nominated_overlay_kernel<2>, grid, dim3(256), 0, ctx->stream, ctx->nomt, ctx->d, ctx->kc,
-                         (const PodRec*)ctx->est.recs, nw, ctx->nom_fit);
+    const dim3 grid((unsigned)((ctx->nom.nomt.nn + 3) / 4));
+    HIPCHK(ctx, hipMemsetAsync(ctx->nom.fit, 0, (size_t)n * 4, ctx->stream));
+    if (ctx->nodes.nsc == 0)
+      hipLaunchKernelGGL(nominated_overlay_kernel<0>, grid, dim3(256), 0, ctx->stream, ctx->nom.nomt, ctx->nodes.d, ctx->kc,
+                         (const PodRec*)ctx->est.recs, nw, ctx->nom.fit);
+    else if (ctx->nodes.nsc == 2)
+      hipLaunchKernelGGL(nominated_overlay_kernel<2>, grid, dim3(256), 0, ctx->stream, ctx->nom.nomt, ctx->nodes.d, ctx->kc,
+                         (const PodRec*)ctx->est.recs, nw, ctx->nom.fit);
     else
-      hipLaunchKernelGGL(nominated_overlay_kernel<4>, grid, dim3(256), 0, ctx->stream, ctx->nomt, ctx->d, ctx->kc,
-                         (const PodRec*)ctx->est.recs, nw, ctx->nom_fit);
-    nom_fit = ctx->nom_fit;
+      hipLaunchKernelGGL(nominated_overlay_kernel<4>, grid, dim3(256), 0, ctx->stream, ctx->nom.nomt, ctx->nodes.d, ctx->kc,
+                         (const PodRec*)ctx->est.recs, nw, ctx->nom.fit);
+    nom_fit = ctx->nom.fit;
   }
-  if (blocks > 0 && ctx->cfg.topology.enable && ctx->est.topo) {
+  if (blocks > 0 && ctx->cfg.topology.enable && ctx->est.topo.get()) {
     // PodTopologySpread / InterPodAffinity: their PreFilter sums, every Filter (theirs folded into the evaluation
     // kernel), then every normalization over the nodes all Filters leave (the topology step's kernels)
     const TopoKArgs ta = topo_args(ctx, ctx->est, nullptr, eb);
     HIPCHK(ctx, launch_topo_sums(ctx->stream, ta));
-    HIPCHK(ctx, launch_eval_debug(ctx->nsc, blocks, ctx->stream, ctx->d, ctx->drv, ctx->ddv, ctx->dnv, ctx->kc,
+    HIPCHK(ctx, launch_eval_debug(ctx->nodes.nsc, blocks, ctx->stream, ctx->nodes.d, ctx->drv.get(), ctx->ddv.get(), ctx->dnv.get(), ctx->kc,
                                   ctx->est.recs, n, dr, ds, dt, draw, dhi, ddraw, ctx->est.stat, dtraw, daraw, &ta,
-                                  kernel_feat(ctx), ctx->numa_w));
+                                  kernel_feat(ctx), ctx->numa.w));
     HIPCHK(ctx, launch_topo_pts(ctx->stream, ta));
     HIPCHK(ctx, launch_topo_norm(ctx->stream, ta));
   } else if (blocks > 0) {
-    HIPCHK(ctx, launch_eval_debug(ctx->nsc, blocks, ctx->stream, ctx->d, ctx->drv, ctx->ddv, ctx->dnv, ctx->kc,
+    HIPCHK(ctx, launch_eval_debug(ctx->nodes.nsc, blocks, ctx->stream, ctx->nodes.d, ctx->drv.get(), ctx->ddv.get(), ctx->dnv.get(), ctx->kc,
                                   ctx->est.recs, n, dr, ds, dt, draw, dhi, ddraw, ctx->est.stat, dtraw, daraw, nullptr,
-                                  kernel_feat(ctx), ctx->numa_w, nom_fit));
+                                  kernel_feat(ctx), ctx->numa.w, nom_fit));
     if (ctx->kc.dev)
       hipLaunchKernelGGL(dev_normalize_debug_kernel, dim3(1), dim3(1024), 0, ctx->stream, n, dr, ddraw, ds, dt,
                          ctx->cfg.deviceshare.plugin_weight);
@@ -5002,7 +4978,7 @@ static int eval_pod_impl(ks_ctx* ctx, const ks_pod_cols* pod, const ks_nominatio
                          uint32_t* reasons, int64_t* scores, int64_t* total) {
   EvBuf eb;
   if (int rc = eval_pod_launch(ctx, pod, who, eb, nom); rc != KS_OK) return rc;
-  const int64_t n = ctx->n;
+  const int64_t n = ctx->nodes.n;
   const uint32_t* dr = eb.dr;
   const int64_t *ds = eb.ds, *dt = eb.dt;
   if (reasons && n) HIPCHK(ctx, hipMemcpyAsync(reasons, dr, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream));
@@ -5041,25 +5017,22 @@ struct SumBuf {
 };
 static int sum_buffers(ks_ctx* ctx, SumBuf& b) {
   static_assert(sizeof(SumOut) % 8 == 0, "the bitmask words follow SumOut");
-  const int64_t n = ctx->n;
+  const int64_t n = ctx->nodes.n;
   b.nwords = (n + 63) / 64;
   b.blocks = (int)((n + kSumThreads - 1) / kSumThreads);
   const size_t host_bytes = sizeof(SumOut) + (size_t)b.nwords * 16;
   const size_t bytes = host_bytes + (size_t)b.blocks * (kSumTop * 12 + kSumBins * 4) + 64;
   if (ctx->sumbuf_bytes < bytes) {
-    dev_free(ctx->sumbuf);
     ctx->sumbuf_bytes = 0;
-    if (dev_alloc(ctx, &ctx->sumbuf, bytes) != KS_OK) return KS_ENOMEM;
+    if (dev_alloc(ctx, ctx->sumbuf, bytes) != KS_OK) return KS_ENOMEM;
     ctx->sumbuf_bytes = bytes;
   }
   if (ctx->sumhost_bytes < host_bytes) {
-    if (ctx->sumhost) (void)hipHostFree(ctx->sumhost);
-    ctx->sumhost = nullptr;
     ctx->sumhost_bytes = 0;
-    HIPCHK(ctx, hipHostMalloc(&ctx->sumhost, host_bytes, hipHostMallocDefault));
+    if (int rc = host_alloc(ctx, ctx->sumhost, host_bytes); rc != KS_OK) return rc;
     ctx->sumhost_bytes = host_bytes;
   }
-  b.out = (SumOut*)ctx->sumbuf;
+  b.out = (SumOut*)ctx->sumbuf.get();
   b.fbits = (uint64_t*)(b.out + 1);
   b.ubits = b.fbits + b.nwords;
   b.part_tot = (int64_t*)(b.ubits + b.nwords);
@@ -5081,7 +5054,7 @@ static int eval_pod_summary_impl(ks_ctx* ctx, const ks_pod_cols* pod, const ks_n
   // the pod's own nominated node, tried first: when it is feasible it is the whole feasible set
   const int32_t only = nom ? nom->nominated_node : -1;
   if (int rc = eval_pod_launch(ctx, pod, who, eb, nom, only); rc != KS_OK) return rc;
-  const int64_t n = ctx->n;
+  const int64_t n = ctx->nodes.n;
   memset(out, 0, sizeof(*out));
   out->best_node = -1;
   out->best_total = -1;
@@ -5099,9 +5072,9 @@ static int eval_pod_summary_impl(ks_ctx* ctx, const ks_pod_cols* pod, const ks_n
   HIPCHK(ctx, hipGetLastError());
   // one copy: the summary and the top rows, and the bitmask words up to the last one asked for
   const size_t words = unresolvable_bits ? 2 * (size_t)sb.nwords : feasible_bits ? (size_t)sb.nwords : 0;
-  HIPCHK(ctx, hipMemcpyAsync(ctx->sumhost, sb.out, sizeof(SumOut) + words * 8, hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(ctx, hipMemcpyAsync(ctx->sumhost.get(), sb.out, sizeof(SumOut) + words * 8, hipMemcpyDeviceToHost, ctx->stream));
   HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-  const SumOut* h = (const SumOut*)ctx->sumhost;
+  const SumOut* h = (const SumOut*)ctx->sumhost.get();
   *out = h->s;
   const size_t rows = (size_t)h->s.top_count;
   if (top_nodes) memcpy(top_nodes, h->top_nodes, rows * 4);
@@ -5267,11 +5240,11 @@ __global__ void unreserve_kernel(UnreserveArgs a) {
 
 int ks_assume(ks_ctx* ctx, const ks_pod_cols* pod, int32_t node, ks_result* out, uint64_t* cpuset, int64_t* numa_alloc) {
   if (!ctx || !pod || !out) return ctx ? (ctx->err = "ks_assume: bad args", KS_EINVAL) : KS_EINVAL;
-  if (!ctx->node_blob) KS_FAIL(ctx, KS_ESTATE, "ks_assume before ks_load_nodes");
-  if (node < 0 || node >= ctx->n) KS_FAIL(ctx, KS_EINVAL, "ks_assume: node %d out of range", node);
-  if (ctx->cfg.quota.enable && pod->quota && !ctx->quota_blob) KS_FAIL(ctx, KS_ESTATE, "ks_assume: quotas not loaded");
+  if (!ctx->nodes.blob.get()) KS_FAIL(ctx, KS_ESTATE, "ks_assume before ks_load_nodes");
+  if (node < 0 || node >= ctx->nodes.n) KS_FAIL(ctx, KS_EINVAL, "ks_assume: node %d out of range", node);
+  if (ctx->cfg.quota.enable && pod->quota && !ctx->quota.blob.get()) KS_FAIL(ctx, KS_ESTATE, "ks_assume: quotas not loaded");
   if (int rc = validate_pods(ctx, pod, 1); rc != KS_OK) return rc;
-  bind_mode(ctx, ctx->val_bind_required);
+  bind_mode(ctx, ctx->staged.val_bind_required);
   HIPCHK(ctx, hipSetDevice(ctx->device));
   if (int rc = commit_attr_set(ctx); rc != KS_OK) return rc;
   if (ensure_stage(ctx, ctx->ast, 1) != KS_OK || ensure_cpuset_bufs(ctx, 1) != KS_OK) return KS_ENOMEM;
@@ -5284,36 +5257,36 @@ int ks_assume(ks_ctx* ctx, const ks_pod_cols* pod, int32_t node, ks_result* out,
     int32_t count;
     uint64_t bound, top;
   } h{(uint32_t)(node >> 6), make_uint2((1u << 6) | (uint32_t)(63 - (node & 63)), 0u), 1, 0ull, 0ull};
-  HIPCHK(ctx, hipMemcpyAsync(ctx->cand_chunk, &h.chunk, 4, hipMemcpyHostToDevice, ctx->stream));
-  HIPCHK(ctx, hipMemcpyAsync(ctx->cand_t, &h.t, 8, hipMemcpyHostToDevice, ctx->stream));
-  HIPCHK(ctx, hipMemcpyAsync(ctx->cand_count, &h.count, 4, hipMemcpyHostToDevice, ctx->stream));
-  HIPCHK(ctx, hipMemcpyAsync(ctx->cand_bound, &h.bound, 8, hipMemcpyHostToDevice, ctx->stream));
-  HIPCHK(ctx, hipMemcpyAsync(ctx->cand_top, &h.top, 8, hipMemcpyHostToDevice, ctx->stream));
-  HIPCHK(ctx, hipMemcpyAsync(ctx->cand_second, &h.top, 8, hipMemcpyHostToDevice, ctx->stream));
-  HIPCHK(ctx, hipMemsetAsync(ctx->cursor, 0, 4, ctx->stream));
-  HIPCHK(ctx, hipMemsetAsync(ctx->dev_M, 0, kNormRows * kMaxBatch * 8, ctx->stream));
-  if (ctx->cpuset_list) {
+  HIPCHK(ctx, hipMemcpyAsync(ctx->cand_chunk.get(), &h.chunk, 4, hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(ctx, hipMemcpyAsync(ctx->cand_t.get(), &h.t, 8, hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(ctx, hipMemcpyAsync(ctx->cand_count.get(), &h.count, 4, hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(ctx, hipMemcpyAsync(ctx->cand_bound.get(), &h.bound, 8, hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(ctx, hipMemcpyAsync(ctx->cand_top.get(), &h.top, 8, hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(ctx, hipMemcpyAsync(ctx->cand_second.get(), &h.top, 8, hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(ctx, hipMemsetAsync(ctx->cursor.get(), 0, 4, ctx->stream));
+  HIPCHK(ctx, hipMemsetAsync(ctx->dev_M.get(), 0, kNormRows * kMaxBatch * 8, ctx->stream));
+  if (ctx->cpuset_list.get()) {
     HIPCHK(ctx, hipMemsetAsync(ctx->cpuset_n, 0, 4, ctx->stream));
     HIPCHK(ctx, hipMemsetAsync(ctx->cpuset_out, 0, sizeof(CpuSet), ctx->stream));
-    HIPCHK(ctx, hipMemsetAsync(ctx->numa_alloc, 0, (size_t)2 * ctx->numa_w * 8, ctx->stream));
+    HIPCHK(ctx, hipMemsetAsync(ctx->numa_alloc, 0, (size_t)2 * ctx->numa.w * 8, ctx->stream));
   }
   CommitArgs ca = commit_args(ctx, ctx->ast, 1, 1);
   ca.force = 1;
   if (ca.topo) ca.topo = 3;  // count the pod's properties on the node
   const CommitPlan& plan = ctx->plan;
-  HIPCHK(ctx, pass_launcher(plan.feat, ctx->nsc, plan.wide).commit(plan.qcache, plan.smem, ctx->stream, ca));
-  if (ctx->cpu_loaded && ctx->n > 0) {
+  HIPCHK(ctx, pass_launcher(plan.feat, ctx->nodes.nsc, plan.wide).commit(plan.qcache, plan.smem, ctx->stream, ca));
+  if (ctx->cpus.loaded && ctx->nodes.n > 0) {
     cpuset_launch(ctx, (const PodRec*)ctx->ast.recs);
     HIPCHK(ctx, hipGetLastError());
   }
   HIPCHK(ctx, hipMemcpyAsync(out, ctx->ast.results, sizeof(ks_result), hipMemcpyDeviceToHost, ctx->stream));
-  const int W = ctx->numa_w;
+  const int W = ctx->numa.w;
   int64_t na[2 * kNumaWide] = {0};
   if (cpuset) {
-    if (ctx->cpuset_list) HIPCHK(ctx, hipMemcpyAsync(cpuset, ctx->cpuset_out, sizeof(CpuSet), hipMemcpyDeviceToHost, ctx->stream));
+    if (ctx->cpuset_list.get()) HIPCHK(ctx, hipMemcpyAsync(cpuset, ctx->cpuset_out, sizeof(CpuSet), hipMemcpyDeviceToHost, ctx->stream));
     else memset(cpuset, 0, sizeof(CpuSet));
   }
-  if (numa_alloc && ctx->cpuset_list)
+  if (numa_alloc && ctx->cpuset_list.get())
     HIPCHK(ctx, hipMemcpyAsync(na, ctx->numa_alloc, (size_t)2 * W * 8, hipMemcpyDeviceToHost, ctx->stream));
   HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
   if (numa_alloc) {
@@ -5323,10 +5296,10 @@ int ks_assume(ks_ctx* ctx, const ks_pod_cols* pod, int32_t node, ks_result* out,
   }
   // the assume wrote pod 0's slots of the batch's cpuset and NUMA-allocation buffers: the last ks_schedule*'s
   // CPU sets are gone, so ks_fetch_cpusets / ks_fetch_numa_alloc refuse until the next schedule
-  ctx->cpusets_clobbered = true;
+  ctx->staged.cpusets_clobbered = true;
   if (out->status == KS_S_SCHEDULED && (out->gpu_minors | out->rdma_minors)) {
-    if (ctx->h_dev_assumed.size() < (size_t)ctx->n) ctx->h_dev_assumed.resize((size_t)ctx->n, 0);
-    ++ctx->h_dev_assumed[(size_t)node];
+    if (ctx->dev.h_assumed.size() < (size_t)ctx->nodes.n) ctx->dev.h_assumed.resize((size_t)ctx->nodes.n, 0);
+    ++ctx->dev.h_assumed[(size_t)node];
   }
   if (out->node != node && out->status == KS_S_SCHEDULED)
     KS_FAIL(ctx, KS_EHIP, "ks_assume: placed on node %d instead of %d", out->node, node);
@@ -5335,44 +5308,44 @@ int ks_assume(ks_ctx* ctx, const ks_pod_cols* pod, int32_t node, ks_result* out,
 
 int ks_unreserve(ks_ctx* ctx, const ks_pod_cols* pod, const ks_result* r, const uint64_t* cpuset, const int64_t* numa_alloc) {
   if (!ctx || !pod || !r) return ctx ? (ctx->err = "ks_unreserve: bad args", KS_EINVAL) : KS_EINVAL;
-  if (!ctx->node_blob) KS_FAIL(ctx, KS_ESTATE, "ks_unreserve before ks_load_nodes");
-  if (r->status != KS_S_SCHEDULED || r->node < 0 || r->node >= ctx->n)
+  if (!ctx->nodes.blob.get()) KS_FAIL(ctx, KS_ESTATE, "ks_unreserve before ks_load_nodes");
+  if (r->status != KS_S_SCHEDULED || r->node < 0 || r->node >= ctx->nodes.n)
     KS_FAIL(ctx, KS_EINVAL, "ks_unreserve: the result is not a placement (status %u, node %d)", r->status, r->node);
   if (int rc = validate_pods(ctx, pod, 1); rc != KS_OK) return rc;
   int32_t gi = -1;
   if (r->reservation >= 0) {
-    if (!ctx->cfg.reservation.enable || (size_t)r->reservation >= ctx->h_rsv_gi.size())
+    if (!ctx->cfg.reservation.enable || (size_t)r->reservation >= ctx->rsv.h_gi.size())
       KS_FAIL(ctx, KS_EINVAL, "ks_unreserve: reservation row %d unknown", r->reservation);
-    gi = ctx->h_rsv_gi[(size_t)r->reservation];
+    gi = ctx->rsv.h_gi[(size_t)r->reservation];
     if (gi < 0) KS_FAIL(ctx, KS_EINVAL, "ks_unreserve: reservation row %d was deleted", r->reservation);
   }
   HIPCHK(ctx, hipSetDevice(ctx->device));
   if (ensure_stage(ctx, ctx->ast, 1) != KS_OK) return KS_ENOMEM;
-  if (!ctx->ures && dev_alloc(ctx, &ctx->ures, 16 + sizeof(CpuSet) + 2 * kNumaWide * 8) != KS_OK) return KS_ENOMEM;
+  if (!ctx->ures.get() && dev_alloc(ctx, ctx->ures, 16 + sizeof(CpuSet) + 2 * kNumaWide * 8) != KS_OK) return KS_ENOMEM;
   if (stage_cols(ctx, ctx->ast, pod, 1) != KS_OK || prep_stage(ctx, ctx->ast, 1) != KS_OK) return KS_EHIP;
-  char* u = (char*)ctx->ures;
+  char* u = (char*)ctx->ures.get();
   int32_t* d_idx = (int32_t*)u;
   uint64_t* d_cs = (uint64_t*)(u + 16);
   int64_t* d_na = (int64_t*)(u + 16 + sizeof(CpuSet));
   const int32_t node = r->node;
   HIPCHK(ctx, hipMemcpyAsync(d_idx, &node, 4, hipMemcpyHostToDevice, ctx->stream));
   if (cpuset) HIPCHK(ctx, hipMemcpyAsync(d_cs, cpuset, sizeof(CpuSet), hipMemcpyHostToDevice, ctx->stream));
-  const int W = ctx->numa_w;
+  const int W = ctx->numa.w;
   int64_t na[2 * kNumaWide] = {0};
   if (numa_alloc)
     for (int k = 0; k < W; ++k)
       for (int q = 0; q < 2; ++q) na[q * W + k] = numa_alloc[k * 2 + q];
   HIPCHK(ctx, hipMemcpyAsync(d_na, na, sizeof(na), hipMemcpyHostToDevice, ctx->stream));
   // the node's reservation base restore follows the reservation's state: out before, back in after
-  const bool rb = gi >= 0 && ctx->rsv_based;
+  const bool rb = gi >= 0 && ctx->rsv.based;
   if (rb && rsv_launch_base(ctx, d_idx, 1, -1, 0) != KS_OK) return KS_EHIP;
   UnreserveArgs ua;
-  ua.d = ctx->d;
-  ua.rv = ctx->rv;
-  ua.dv = ctx->dv;
-  ua.nv = ctx->nv;
-  ua.cpu = ctx->cpu;
-  ua.q = ctx->q;
+  ua.d = ctx->nodes.d;
+  ua.rv = ctx->rsv.rv;
+  ua.dv = ctx->dev.dv;
+  ua.nv = ctx->numa.nv;
+  ua.cpu = ctx->cpus.cpu;
+  ua.q = ctx->quota.q;
   ua.pq = ctx->ast.pq;
   ua.pod = ctx->ast.recs;
   ua.pstat = ctx->ast.stat;
@@ -5383,33 +5356,33 @@ int ks_unreserve(ks_ctx* ctx, const ks_pod_cols* pod, const ks_result* r, const 
   ua.rmin = r->rdma_minors;
   ua.cpuset = cpuset ? d_cs : nullptr;
   ua.nalloc = numa_alloc ? d_na : nullptr;
-  ua.quota = ctx->kc.quota_enable && ctx->quota_blob;
-  ua.dev = ctx->kc.dev && ctx->dev_loaded;
-  ua.cpu_loaded = ctx->cpu_loaded;
-  ua.numa_pol = ctx->kc.numa_pol && ctx->numa_blob;
+  ua.quota = ctx->kc.quota_enable && ctx->quota.blob.get();
+  ua.dev = ctx->kc.dev && ctx->dev.loaded;
+  ua.cpu_loaded = ctx->cpus.loaded;
+  ua.numa_pol = ctx->kc.numa_pol && ctx->numa.blob.get();
   ua.ratio_amp = ctx->cfg.numa.enable;
-  ua.numa_w = ctx->numa_w;
-  ua.topo = ctx->cfg.topology.enable ? ctx->ast.topo : nullptr;
-  ua.topo_props = ctx->ast.topo_props;
-  ua.topo_count = ctx->topo_count;
-  ua.topo_npad = ctx->npad;
+  ua.numa_w = ctx->numa.w;
+  ua.topo = ctx->cfg.topology.enable ? ctx->ast.topo.get() : nullptr;
+  ua.topo_props = ctx->ast.topo_props.get();
+  ua.topo_count = ctx->topo.count;
+  ua.topo_npad = ctx->nodes.npad;
   hipLaunchKernelGGL(unreserve_kernel, dim3(1), dim3(64), 0, ctx->stream, ua);
   HIPCHK(ctx, hipGetLastError());
   if (rb && rsv_launch_base(ctx, d_idx, 1, +1, 1) != KS_OK) return KS_EHIP;
   HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-  if ((r->gpu_minors | r->rdma_minors) && (size_t)node < ctx->h_dev_assumed.size() && ctx->h_dev_assumed[(size_t)node] > 0)
-    --ctx->h_dev_assumed[(size_t)node];
+  if ((r->gpu_minors | r->rdma_minors) && (size_t)node < ctx->dev.h_assumed.size() && ctx->dev.h_assumed[(size_t)node] > 0)
+    --ctx->dev.h_assumed[(size_t)node];
   return KS_OK;
 }
 
 int ks_fetch_numa_alloc(ks_ctx* ctx, int64_t* out, int32_t p) {
   if (!ctx || (p > 0 && !out) || p < 0) return ctx ? (ctx->err = "ks_fetch_numa_alloc: bad args", KS_EINVAL) : KS_EINVAL;
-  if (p > ctx->np) KS_FAIL(ctx, KS_EINVAL, "ks_fetch_numa_alloc: %d pods requested, %d scheduled", p, ctx->np);
-  if (p > 0 && ctx->cpusets_clobbered) KS_FAIL(ctx, KS_ESTATE, "ks_fetch_numa_alloc: a ks_assume since the last schedule overwrote it");
+  if (p > ctx->staged.np) KS_FAIL(ctx, KS_EINVAL, "ks_fetch_numa_alloc: %d pods requested, %d scheduled", p, ctx->staged.np);
+  if (p > 0 && ctx->staged.cpusets_clobbered) KS_FAIL(ctx, KS_ESTATE, "ks_fetch_numa_alloc: a ks_assume since the last schedule overwrote it");
   if (p == 0) return KS_OK;
   memset(out, 0, (size_t)p * KS_MAX_NUMA * 2 * 8);
   if (!ctx->numa_alloc || ctx->cpuset_cap < p) return KS_OK;
-  const int W = ctx->numa_w;
+  const int W = ctx->numa.w;
   std::vector<int64_t> h((size_t)p * 2 * W);
   HIPCHK(ctx, hipMemcpyAsync(h.data(), ctx->numa_alloc, h.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
   HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
@@ -5421,28 +5394,28 @@ int ks_fetch_numa_alloc(ks_ctx* ctx, int64_t* out, int32_t p) {
 
 int ks_read_nodes(ks_ctx* ctx, ks_node_state* o) {
   if (!ctx || !o) return ctx ? (ctx->err = "ks_read_nodes: bad args", KS_EINVAL) : KS_EINVAL;
-  if (!ctx->node_blob) KS_FAIL(ctx, KS_ESTATE, "ks_read_nodes before ks_load_nodes");
-  const size_t n = (size_t)ctx->n;
+  if (!ctx->nodes.blob.get()) KS_FAIL(ctx, KS_ESTATE, "ks_read_nodes before ks_load_nodes");
+  const size_t n = (size_t)ctx->nodes.n;
   auto cp = [&](void* h, const void* d, size_t w) -> hipError_t {
     if (!h || !n) return hipSuccess;
     return hipMemcpyAsync(h, d, n * w, hipMemcpyDeviceToHost, ctx->stream);
   };
   // the columns hold the reservation base restore: the reference's NodeInfo is computed into a scratch copy of
   // the restored columns (the live columns are never touched)
-  DevNodes v = ctx->d;
-  if (ctx->rsv_based && n) {
+  DevNodes v = ctx->nodes.d;
+  if (ctx->rsv.based && n) {
     // [5 + KS_MAX_SCALARS][npad]: sized by this node table's padded count (ks_load_nodes frees it with the old table)
-    if (!ctx->rdscratch && dev_alloc(ctx, &ctx->rdscratch, (size_t)ctx->npad * 8 * (5 + KS_MAX_SCALARS)) != KS_OK)
+    if (!ctx->nodes.rdscratch.get() && dev_alloc(ctx, ctx->nodes.rdscratch, (size_t)ctx->nodes.npad * 8 * (5 + KS_MAX_SCALARS)) != KS_OK)
       return KS_ENOMEM;
-    int64_t* sc = (int64_t*)ctx->rdscratch;
+    int64_t* sc = (int64_t*)ctx->nodes.rdscratch.get();
     int64_t** cols[5 + KS_MAX_SCALARS] = {&v.req_cpu, &v.req_mem, &v.req_eph, &v.nz_cpu, &v.nz_mem};
     for (int k = 0; k < KS_MAX_SCALARS; ++k) cols[5 + k] = &v.req_sc[k];
     for (int c = 0; c < 5 + KS_MAX_SCALARS; ++c) {
-      int64_t* dst = sc + (size_t)c * ctx->npad;
+      int64_t* dst = sc + (size_t)c * ctx->nodes.npad;
       HIPCHK(ctx, hipMemcpyAsync(dst, *cols[c], n * 8, hipMemcpyDeviceToDevice, ctx->stream));
       *cols[c] = dst;
     }
-    hipLaunchKernelGGL(rsv_base_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, v, ctx->rv,
+    hipLaunchKernelGGL(rsv_base_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, v, ctx->rsv.rv,
                        (const int32_t*)nullptr, (int64_t)n, (int64_t)-1, 0);
     HIPCHK(ctx, hipGetLastError());
   }
@@ -5458,16 +5431,16 @@ int ks_read_nodes(ks_ctx* ctx, ks_node_state* o) {
   HIPCHK(ctx, cp(o->la_prod_term_milli_cpu, v.la_pterm_cpu, 8));
   HIPCHK(ctx, cp(o->la_prod_term_memory, v.la_pterm_mem, 8));
   HIPCHK(ctx, cp(o->host_ports, v.host_ports, 8));
-  for (size_t q = 0; o->topo_count && q < ctx->topo_count_v.size(); ++q)
-    HIPCHK(ctx, cp(o->topo_count + q * n, ctx->topo_count_v[q], 4));
+  for (size_t q = 0; o->topo_count && q < ctx->topo.count_v.size(); ++q)
+    HIPCHK(ctx, cp(o->topo_count + q * n, ctx->topo.count_v[q], 4));
   HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
   return KS_OK;
 }
 
 int ks_read_quota_used(ks_ctx* ctx, int64_t* used) {
   if (!ctx || !used) return ctx ? (ctx->err = "ks_read_quota_used: bad args", KS_EINVAL) : KS_EINVAL;
-  if (!ctx->quota_blob || ctx->q.q == 0) return KS_OK;
-  HIPCHK(ctx, hipMemcpyAsync(used, ctx->q.used, (size_t)ctx->q.q * KS_QUOTA_DIMS * 8, hipMemcpyDeviceToHost, ctx->stream));
+  if (!ctx->quota.blob.get() || ctx->quota.q.q == 0) return KS_OK;
+  HIPCHK(ctx, hipMemcpyAsync(used, ctx->quota.q.used, (size_t)ctx->quota.q.q * KS_QUOTA_DIMS * 8, hipMemcpyDeviceToHost, ctx->stream));
   HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
   return KS_OK;
 }
@@ -5477,9 +5450,9 @@ int ks_read_quota_used(ks_ctx* ctx, int64_t* used) {
 int ks_load_node_pods(ks_ctx* ctx, const ks_node_pod_cols* pc, int64_t m, const int32_t* pdb_allowed, int32_t npdb) {
   if (!ctx || !pc || m < 0 || npdb < 0 || (m > 0 && !pc->node) || (npdb > 0 && !pdb_allowed))
     return ctx ? (ctx->err = "ks_load_node_pods: bad args", KS_EINVAL) : KS_EINVAL;
-  if (!ctx->node_blob) KS_FAIL(ctx, KS_ESTATE, "ks_load_node_pods before ks_load_nodes");
+  if (!ctx->nodes.blob.get()) KS_FAIL(ctx, KS_ESTATE, "ks_load_node_pods before ks_load_nodes");
   if (m >= ((int64_t)1 << 31)) KS_FAIL(ctx, KS_EINVAL, "ks_load_node_pods: too many pods");
-  const int64_t n = ctx->n;
+  const int64_t n = ctx->nodes.n;
   std::vector<int64_t> beg((size_t)n + 1, 0);
   for (int64_t i = 0; i < m; ++i) {
     const int32_t nd = pc->node[i];
@@ -5559,12 +5532,11 @@ int ks_load_node_pods(ks_ctx* ctx, const ks_node_pod_cols* pc, int64_t m, const 
   }
   if (npdb) memcpy(h.data() + o_pdba, pdb_allowed, (size_t)npdb * 4);
   HIPCHK(ctx, hipSetDevice(ctx->device));
-  dev_free(ctx->npod_blob);
-  if (dev_alloc(ctx, &ctx->npod_blob, off) != KS_OK) return KS_ENOMEM;
-  HIPCHK(ctx, hipMemcpyAsync(ctx->npod_blob, h.data(), off, hipMemcpyHostToDevice, ctx->stream));
+  if (dev_alloc(ctx, ctx->npods.blob, off) != KS_OK) return KS_ENOMEM;
+  HIPCHK(ctx, hipMemcpyAsync(ctx->npods.blob.get(), h.data(), off, hipMemcpyHostToDevice, ctx->stream));
   HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-  unsigned char* b = (unsigned char*)ctx->npod_blob;
-  DevNodePods& t = ctx->npt;
+  unsigned char* b = (unsigned char*)ctx->npods.blob.get();
+  DevNodePods& t = ctx->npods.npt;
   t.beg = (const int64_t*)(b + o_beg);
   t.prio = (const int32_t*)(b + o_prio);
   t.start = (const int64_t*)(b + o_start);
@@ -5577,12 +5549,12 @@ int ks_load_node_pods(ks_ctx* ctx, const ks_node_pod_cols* pc, int64_t m, const 
   t.pdb_allowed = (const int32_t*)(b + o_pdba);
   t.m = (int64_t)mm;
   t.npdb = npdb;
-  ctx->pre_cand = (PreemptCand*)(b + o_cand);
-  ctx->pre_vrank = (int32_t*)(b + o_vrank);
-  ctx->pre_status = (uint8_t*)(b + o_status);
-  ctx->pre_out = (PreemptOut*)(b + o_out);
-  ctx->pre_victims = (int32_t*)(b + o_vic);
-  ctx->npod_slots = maxc <= 64 ? 1 : (maxc <= 128 ? 2 : 4);
+  ctx->npods.cand = (PreemptCand*)(b + o_cand);
+  ctx->npods.vrank = (int32_t*)(b + o_vrank);
+  ctx->npods.status = (uint8_t*)(b + o_status);
+  ctx->npods.out = (PreemptOut*)(b + o_out);
+  ctx->npods.victims = (int32_t*)(b + o_vic);
+  ctx->npods.slots = maxc <= 64 ? 1 : (maxc <= 128 ? 2 : 4);
   return KS_OK;
 }
 
@@ -5598,17 +5570,17 @@ int ks_preempt_nominated(ks_ctx* ctx, const ks_pod_cols* pod, int32_t priority, 
                          int32_t victims_cap, uint8_t* node_status) {
   if (!ctx || !pod || !out || victims_cap < 0 || (victims_cap > 0 && !victims))
     return ctx ? (ctx->err = "ks_preempt: bad args", KS_EINVAL) : KS_EINVAL;
-  if (!ctx->npod_blob) KS_FAIL(ctx, KS_ESTATE, "ks_preempt before ks_load_node_pods");
-  if (!ctx->cfg.quota.enable || !ctx->quota_blob || ctx->q.q == 0)
+  if (!ctx->npods.blob.get()) KS_FAIL(ctx, KS_ESTATE, "ks_preempt before ks_load_node_pods");
+  if (!ctx->cfg.quota.enable || !ctx->quota.blob.get() || ctx->quota.q.q == 0)
     KS_FAIL(ctx, KS_EUNSUPPORTED, "ks_preempt: the ElasticQuota PostFilter needs ElasticQuota and a loaded quota table");
   if (ctx->kc.rsv || ctx->kc.numa || ctx->kc.dev || (ctx->kc.ports & 1))
     KS_FAIL(ctx, KS_EUNSUPPORTED, "ks_preempt: Reservation / NodeNUMAResource / DeviceShare / NodePorts filters read the "
                                   "node's other pods (their PreFilter extensions are not modelled)");
   const int32_t q = pod->quota ? pod->quota[0] : -1;
-  if (q < 0 || q >= ctx->q.q)
+  if (q < 0 || q >= ctx->quota.q.q)
     KS_FAIL(ctx, KS_EUNSUPPORTED, "ks_preempt: the pod has no quota row (the reference's cloned PostFilterState has no "
                                   "QuotaInfo then)");
-  if (nominated < -1 || nominated >= ctx->n) KS_FAIL(ctx, KS_EINVAL, "ks_preempt: nominated node %d out of range", nominated);
+  if (nominated < -1 || nominated >= ctx->nodes.n) KS_FAIL(ctx, KS_EINVAL, "ks_preempt: nominated node %d out of range", nominated);
   if (ctx->cfg.topology.enable && pod->topo_flags && (pod->topo_flags[0] & KS_TOPO_DYN))
     KS_FAIL(ctx, KS_EUNSUPPORTED, "ks_preempt: the dry runs do not model PodTopologySpread / InterPodAffinity (the pod "
                                   "has topology terms)");
@@ -5616,23 +5588,22 @@ int ks_preempt_nominated(ks_ctx* ctx, const ks_pod_cols* pod, int32_t priority, 
   HIPCHK(ctx, hipSetDevice(ctx->device));
   if (ensure_stage(ctx, ctx->est, 1) != KS_OK) return KS_ENOMEM;
   if (stage_cols(ctx, ctx->est, pod, 1) != KS_OK || prep_stage(ctx, ctx->est, 1) != KS_OK) return KS_EHIP;
-  const int64_t n = ctx->n;
+  const int64_t n = ctx->nodes.n;
   uint8_t* dunres = nullptr;
   if (unresolvable && n > 0) {
     // the caller's per-node statuses, staged through the ks_eval_pod scratch
     if (ctx->evbuf_bytes < (size_t)n) {
-      dev_free(ctx->evbuf);
       ctx->evbuf_bytes = 0;
-      if (dev_alloc(ctx, &ctx->evbuf, (size_t)n) != KS_OK) return KS_ENOMEM;
+      if (dev_alloc(ctx, ctx->evbuf, (size_t)n) != KS_OK) return KS_ENOMEM;
       ctx->evbuf_bytes = (size_t)n;
     }
-    dunres = (uint8_t*)ctx->evbuf;
+    dunres = (uint8_t*)ctx->evbuf.get();
     HIPCHK(ctx, hipMemcpyAsync(dunres, unresolvable, (size_t)n, hipMemcpyHostToDevice, ctx->stream));
   }
   PreemptArgs a;
-  a.dn = ctx->dnodes;
-  a.t = ctx->npt;
-  a.q = ctx->q;
+  a.dn = ctx->dnodes.get();
+  a.t = ctx->npods.npt;
+  a.q = ctx->quota.q;
   a.pq = ctx->est.pq;
   a.c = ctx->kc;
   a.pod = ctx->est.recs;
@@ -5640,15 +5611,15 @@ int ks_preempt_nominated(ks_ctx* ctx, const ks_pod_cols* pod, int32_t priority, 
   a.prio = priority;
   a.pflags = flags;
   a.nominated = nominated;
-  a.nom = ctx->nomt;  // (beg == nullptr: no table, the dry runs as without one)
+  a.nom = ctx->nom.nomt;  // (beg == nullptr: no table, the dry runs as without one)
   a.self_id = self_id;
   a.unresolvable = dunres;
   a.n = n;
-  a.cand = ctx->pre_cand;
-  a.vrank = ctx->pre_vrank;
-  a.status = ctx->pre_status;
-  a.out = ctx->pre_out;
-  a.victims = ctx->pre_victims;
+  a.cand = ctx->npods.cand;
+  a.vrank = ctx->npods.vrank;
+  a.status = ctx->npods.status;
+  a.out = ctx->npods.out;
+  a.victims = ctx->npods.victims;
   // with ks_set_profile on: the dry-run kernel in stats.sweep_ms, the selection in stats.select_ms
   const bool prof = ctx->cfg.profile != 0;
   hipEvent_t e0 = prof ? take_event(ctx, 0) : nullptr, e1 = prof ? take_event(ctx, 1) : nullptr,
@@ -5656,8 +5627,8 @@ int ks_preempt_nominated(ks_ctx* ctx, const ks_pod_cols* pod, int32_t priority, 
   if (prof) HIPCHK(ctx, hipEventRecord(e0, ctx->stream));
   if (n > 0) {
     const dim3 grid((unsigned)((n + 3) / 4)), block(256);
-    if (ctx->npod_slots == 1) hipLaunchKernelGGL(preempt_dry_run_kernel<1>, grid, block, 0, ctx->stream, a);
-    else if (ctx->npod_slots == 2) hipLaunchKernelGGL(preempt_dry_run_kernel<2>, grid, block, 0, ctx->stream, a);
+    if (ctx->npods.slots == 1) hipLaunchKernelGGL(preempt_dry_run_kernel<1>, grid, block, 0, ctx->stream, a);
+    else if (ctx->npods.slots == 2) hipLaunchKernelGGL(preempt_dry_run_kernel<2>, grid, block, 0, ctx->stream, a);
     else hipLaunchKernelGGL(preempt_dry_run_kernel<4>, grid, block, 0, ctx->stream, a);
   }
   if (prof) HIPCHK(ctx, hipEventRecord(e1, ctx->stream));
@@ -5671,11 +5642,11 @@ int ks_preempt_nominated(ks_ctx* ctx, const ks_pod_cols* pod, int32_t priority, 
     int32_t v[kPreemptMaxPods];
   } rb;
   static_assert(sizeof(PreemptOut) % 16 != 0, "PreemptOut padding");
-  const size_t rbytes = (size_t)((const unsigned char*)ctx->pre_victims - (const unsigned char*)ctx->pre_out) +
+  const size_t rbytes = (size_t)((const unsigned char*)ctx->npods.victims - (const unsigned char*)ctx->npods.out) +
                         (size_t)kPreemptMaxPods * 4;
   if (rbytes != sizeof(rb)) KS_FAIL(ctx, KS_EHIP, "ks_preempt: read-back layout");
-  HIPCHK(ctx, hipMemcpyAsync(&rb, ctx->pre_out, rbytes, hipMemcpyDeviceToHost, ctx->stream));
-  if (node_status && n > 0) HIPCHK(ctx, hipMemcpyAsync(node_status, ctx->pre_status, (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(ctx, hipMemcpyAsync(&rb, ctx->npods.out, rbytes, hipMemcpyDeviceToHost, ctx->stream));
+  if (node_status && n > 0) HIPCHK(ctx, hipMemcpyAsync(node_status, ctx->npods.status, (size_t)n, hipMemcpyDeviceToHost, ctx->stream));
   HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
   const PreemptOut o = rb.o;
   const int32_t nv = std::min(o.nvict, victims_cap);
@@ -5694,7 +5665,7 @@ int ks_preempt_nominated(ks_ctx* ctx, const ks_pod_cols* pod, int32_t priority, 
   // algorithmic bytes of the dry-run launch: every node's pod positions (priority, start, flags, quota, 4 PDB, 7 request
   // and 8 quota-request words: 160 B) and node words (allocatable + requested x 7, pod count, allowed, LoadAware bits;
   // the taint / label words with the dictionary plugins) once, the per-node outcome written
-  ctx->stats.sweep_bytes = ctx->npt.m * 160 + n * (int64_t)(7 * 16 + 12 + (ctx->kc.stat ? 16 : 0) + sizeof(PreemptCand) + 1);
+  ctx->stats.sweep_bytes = ctx->npods.npt.m * 160 + n * (int64_t)(7 * 16 + 12 + (ctx->kc.stat ? 16 : 0) + sizeof(PreemptCand) + 1);
   out->node = o.node;
   out->status = o.status;
   out->num_victims = o.nvict;
@@ -5743,7 +5714,7 @@ int ks_shard_init_loopback(ks_ctx* const* ctxs, int32_t nranks, int32_t virtual_
     if (!ctxs[r]) return KS_EINVAL;
     for (int32_t q = 0; q < r; ++q)
       if (ctxs[q] == ctxs[r]) KS_FAIL(ctxs[r], KS_EINVAL, "ks_shard_init_loopback: a context is given twice");
-    if (ctxs[r]->n != ctxs[0]->n || ctxs[r]->k != ctxs[0]->k || ctxs[r]->batch != ctxs[0]->batch)
+    if (ctxs[r]->nodes.n != ctxs[0]->nodes.n || ctxs[r]->k != ctxs[0]->k || ctxs[r]->batch != ctxs[0]->batch)
       KS_FAIL(ctxs[r], KS_EINVAL, "ks_shard_init_loopback: the ranks must load the same node count, batch and candidates");
   }
   LoopGroup* g = new LoopGroup();
@@ -5757,9 +5728,7 @@ int ks_shard_init_loopback(ks_ctx* const* ctxs, int32_t nranks, int32_t virtual_
       return rc;
     };
     if (int rc = ks_shard_init(ctx, 1, 0, nullptr, 1); rc != KS_OK) return undo(rc);
-    void* p = nullptr;
-    if (dev_alloc(ctx, &p, (size_t)nranks * kNormRows * kMaxBatch * 8) != KS_OK) return undo(KS_ENOMEM);
-    ctx->loop_scratch = (unsigned long long*)p;
+    if (dev_alloc(ctx, ctx->loop_scratch, (size_t)nranks * kNormRows * kMaxBatch * 8) != KS_OK) return undo(KS_ENOMEM);
     for (auto& pr : ctx->lev)
       for (hipEvent_t& e : pr)
         if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) {

@@ -154,6 +154,31 @@ def test_fold_is_exact(oracle_lib):
     assert np.array_equal(o2.read_reservation_devices(), o1.read_reservation_devices())
 
 
+def test_restore_of_every_table_premise(oracle_lib):
+    """test_restore_returns_every_table_at_once dirties every table between ks_checkpoint and ks_restore with `rest`:
+    after `first`, `rest` must commit into quotas, devices (RDMA too), cpusets, a reservation that holds devices and a
+    NUMA-policy node, and the workload must have device pods left to ks_assume"""
+    w, first, rest, _ = ru.single_table()
+    o = oracle_of(oracle_lib, w.cfg, w)
+    o.schedule(first)
+    before = (o.read_quota_used().copy(), [x.copy() for x in o.read_devices()], [x.copy() for x in o.read_cpu_state()],
+              [x.copy() for x in o.read_numa_nodes()], [x.copy() for x in o.read_reservations()],
+              o.read_reservation_devices().copy())
+    got = o.schedule(rest)
+    ok = placed(got)
+    in_dev_rsv = ok & np.isin(got["reservation"], ru.device_rows(w)) & (got["gpu_minors"] != 0)
+    assert in_dev_rsv.sum() >= 1, "no pod of rest takes devices from a reservation that holds them"
+    on_policy = ok & (ru.policy_of(w.nodes)[np.where(ok, got["node"], 0)] != 0)
+    assert on_policy.sum() >= 1, "no pod of rest lands on a NUMA-policy node"
+    assert not np.array_equal(o.read_quota_used(), before[0])
+    assert all(not np.array_equal(x, y) for x, y in zip(o.read_devices(), before[1])), "devices incl. RDMA"
+    assert not np.array_equal(o.read_cpu_state()[0], before[2][0])
+    assert not np.array_equal(o.read_numa_nodes()[0], before[3][0])
+    assert all(not np.array_equal(x, y) for x, y in zip(o.read_reservations(), before[4]))
+    assert not np.array_equal(o.read_reservation_devices(), before[5])
+    assert ((rest.gpu_core > 0) | (rest.gpu_memory_ratio > 0)).sum() >= 10
+
+
 def test_second_tables_differ_and_load(oracle_lib):
     w, first, rest, other = ru.single_table()
     t2 = ru.second_tables(w, other)

@@ -6,7 +6,7 @@ output), compared exactly -- placements, statuses, scores, nominated reservation
 table's read-back, ks_eval_pod on five pods and ks_eval_pod_summary on one.
 
 The scenarios' workloads come from reuse_util.py; test_context_reuse_premises.py shows on the oracle alone that
-each reaches the cache or buffer it is about (DESIGN.md §7b lists them per ks_ctx member)."""
+each reaches the cache or buffer it is about (DESIGN.md §7b lists them per table struct of ks_ctx)."""
 import numpy as np
 import pytest
 
@@ -317,6 +317,78 @@ def test_single_table_reload(runtime, oracle_lib, committed, table):
             assert (got["reservation"] == -1).all()
     finally:
         ev.close()
+
+
+def read_backs(ev):
+    """every table's read-back, by name"""
+    out = {f"nodes.{k}": v.copy() for k, v in ev.read_nodes().as_dict().items()}
+    out["quota used"] = ev.read_quota_used().copy()
+    for k, v in zip(("used_core", "used_memory", "used_ratio", "used_rdma"), ev.read_devices()):
+        out[f"devices.{k}"] = v.copy()
+    for k, v in zip(("allocated", "assigned"), ev.read_reservations()):
+        out[f"reservations.{k}"] = v.copy()
+    out["reservations.devices"] = ev.read_reservation_devices().copy()
+    for k, v in zip(("allocated", "excl_pcpu", "excl_numa"), ev.read_cpu_state()):
+        out[f"cpu_state.{k}"] = v.copy()
+    for k, v in zip(("used_cpu", "used_memory"), ev.read_numa_nodes()):
+        out[f"numa_nodes.{k}"] = v.copy()
+    return out
+
+
+def assume_a_device_pod(ev, pods):
+    """ks_assume of the first device pod of `pods` that still fits somewhere: (its node, the pod)"""
+    from test_gpu_assume import pick
+
+    for i in np.flatnonzero((pods.gpu_core > 0) | (pods.gpu_memory_ratio > 0)):
+        pod = pods.rows([int(i)])
+        node = pick(ev.eval_pod(pod)[2])
+        if node < 0:
+            continue
+        r, _, _ = ev.assume(pod, node)
+        assert r[0]["status"] == abi.KS_S_SCHEDULED and (r[0]["gpu_minors"] != 0 or r[0]["rdma_minors"] != 0)
+        return node
+    raise AssertionError("no device pod fits any node")
+
+
+def test_restore_returns_every_table_at_once(runtime, oracle_lib, committed):
+    """ks_restore brings back nodes, quotas, devices, reservations with their devices, CPU state and NUMA nodes
+    together, and the host's record of assumed device pods: after a checkpoint, 300 more commits and a ks_assume,
+    every read-back equals the one taken before the checkpoint, the context equals a fresh oracle on the tables as
+    they stood then, and all of it a second time (a restore does not use the checkpoint up).
+    test_context_reuse_premises.py::test_restore_of_every_table_premise shows that the commits reach every table."""
+    from test_gpu_deltas import dev_rows
+
+    w, first, rest, _, f, _ = committed
+    t = tables_of(w)
+    ev = runtime.Evaluator(w.cfg, w.nodes.copy(), **w.tables())
+    orc = fresh(oracle_lib, w.cfg, w)
+    try:
+        assert_same_results(ev.schedule(first), orc.schedule(first), "first 150")
+        same_tables(ev, orc, t, "first 150")
+        before = read_backs(ev)
+        for rnd in ("first restore", "second restore"):
+            if rnd == "second restore":  # the context is past `rest` again: the first checkpoint still holds
+                ev.restore()
+                for k, v in read_backs(ev).items():
+                    assert np.array_equal(v, before[k]), f"restore from the used checkpoint: {k}"
+            ev.checkpoint()
+            ev.schedule(rest)
+            node = assume_a_device_pod(ev, w.pods)
+            idx = np.array([node], np.int32)
+            with pytest.raises(runtime.KsError):  # (the node holds an assumed device pod)
+                ev.update_devices(idx, dev_rows(f.devices, idx))
+            ev.restore()
+            for k, v in read_backs(ev).items():
+                assert np.array_equal(v, before[k]), f"{rnd}: {k}"
+            ev.update_devices(idx, dev_rows(f.devices, idx))  # the rows it has: accepted, the assumed pod is forgotten
+            of = fresh(oracle_lib, w.cfg, f)
+            try:
+                same_as_fresh(ev, of, rest, tables_of(f), rnd)
+            finally:
+                of.close()
+    finally:
+        ev.close()
+        orc.close()
 
 
 def test_dependent_tables_load_in_any_order(runtime, oracle_lib):
