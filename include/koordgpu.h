@@ -1045,7 +1045,8 @@ typedef struct ks_nomination {
  * PodTopologySpread / InterPodAffinity, NodeNUMAResource, DeviceShare, Reservation (the set ks_preempt models is Fit,
  * LoadAware, ElasticQuota, BalancedAllocation, TaintToleration, NodeAffinity; of these only Fit's verdict changes with
  * the added pods).  While a non-empty table is loaded the entry points that carry no priority -- ks_schedule,
- * ks_stage_pods, ks_schedule_staged, ks_eval_pod, ks_eval_pod_debug, ks_eval_pod_summary -- answer KS_EUNSUPPORTED
+ * ks_stage_pods, ks_schedule_staged of a batch ks_stage_pods staged, ks_eval_pod, ks_eval_pod_debug,
+ * ks_eval_pod_summary -- answer KS_EUNSUPPORTED
  * instead of ignoring it; with an empty or absent table every entry point behaves as before.  ks_checkpoint /
  * ks_restore cover the table. */
 int ks_load_nominated(ks_ctx *ctx, const ks_nominated_cols *cols, int64_t m, size_t sizeof_cols);
@@ -1069,6 +1070,28 @@ int ks_eval_pod_summary_nominated(ks_ctx *ctx, const ks_pod_cols *pod, const ks_
                                   uint32_t unresolvable_mask, int32_t top_n, ks_pod_summary *out, int32_t *top_nodes,
                                   int64_t *top_totals, int64_t *top_scores, uint64_t *feasible_bits,
                                   uint64_t *unresolvable_bits);
+/* ---- the batched queue with a nominated table loaded (DESIGN.md §2.12a "queue") ----
+ * ks_schedule / ks_stage_pods with one ks_nomination per pod (who[p]: priority, own nominated node or -1, own table id
+ * or -1).  Pods are taken in queue order exactly as if each were scheduled alone with ks_eval_pod_summary_nominated +
+ * ks_assume: ElasticQuota admission as in ks_schedule; a pod's own nominated node is tried first and, when it passes
+ * the Filters, is its only feasible node; otherwise on every node the live rows with priority >= the pod's and another
+ * id are added before NodeResourcesFit, scores are the nodes' own over the nodes that stay feasible, ties go to the
+ * lowest node row.  A pod that reserves has its own row retired at once (upstream assume ->
+ * DeleteNominatedPodIfExists): no later pod of the queue counts it, and when the call returns the row is gone from the
+ * table (ks_delete_nominated of it is the documented no-op; a later ks_eval_pod_nominated sees the reduced table).  A
+ * pod that ends unschedulable or is rejected by its quota keeps its row.  After ks_stage_pods_nominated,
+ * ks_schedule_staged and ks_fetch_results work with a table loaded; ks_schedule / ks_stage_pods keep refusing one.
+ * With no table or an empty one the results are those of ks_schedule.
+ * KS_EINVAL: a nominated_node outside [-1, n), a self_id below -1, the same self_id >= 0 twice in one queue.
+ * KS_EUNSUPPORTED: node sharding (ks_shard_init*) together with a non-empty table.  Passes are not pipelined while a
+ * table is loaded, whatever ks_set_pipeline says (ks_stats.pipelined = 0); the general commit kernel runs.
+ * ks_stats: cut_passes also counts the passes that ended in front of an owner pod (self_id >= 0 or nominated_node
+ * >= 0) or behind a Reserve onto a node with live rows; diag[4] = passes that scheduled an owner pod alone,
+ * diag[5] = rows retired. */
+int ks_stage_pods_nominated(ks_ctx *ctx, const ks_pod_cols *pods, int32_t p, const ks_nomination *who /* [p] */);
+int ks_schedule_nominated(ks_ctx *ctx, const ks_pod_cols *pods, int32_t p, const ks_nomination *who /* [p] */,
+                          ks_result *out);
+
 /* ks_preempt whose dry runs see the nominated table: every Fit check inside SelectVictimsOnNode (after the potential
  * victims are removed and after each reprieve) runs on Requested and pod count plus the node's nominated rows of
  * priority >= `priority`, the row with id self_id (the preemptor's own earlier nomination, -1 = none) excluded.  The

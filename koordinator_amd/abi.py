@@ -532,6 +532,8 @@ EXPORTED_SYMBOLS = [
     "ks_eval_pod_nominated",
     "ks_eval_pod_summary_nominated",
     "ks_preempt_nominated",
+    "ks_stage_pods_nominated",
+    "ks_schedule_nominated",
 ]
 KS_SHARD_ID_BYTES = 128
 

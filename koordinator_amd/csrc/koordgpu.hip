@@ -27,6 +27,8 @@
 #include <cstring>
 #include <mutex>
 #include <string>
+#include <unordered_map>
+#include <unordered_set>
 #include <vector>
 
 #include <rccl/rccl.h>
@@ -1199,6 +1201,15 @@ struct NomTable {
   DevPtr<> blob;                   // the CSR table, then the overlay's output
   DevNominated nomt{};             // beg == nullptr: no table
   uint32_t* fit = nullptr;         // [n] nominated_overlay_kernel's Fit reason bits (view into blob)
+  // the batched queue (ks_stage_pods_nominated): the staged pods' nominations, and the queue table of the running call
+  // (built from h_rows at every ks_schedule_staged: the rows a call retires leave h_rows after it)
+  std::vector<ks_nomination> q_who;  // [staged pods]
+  bool q_staged = false;             // the staged batch came with nominations
+  DevPtr<> qblob;
+  DevNomQueue q{};                   // views into qblob
+  DevNomQueue* dq = nullptr;         // its device copy (the NOM kernels' argument)
+  bool q_on = false;                 // this schedule call runs the NOM variants
+  int32_t q_owners = 0;              // owner pods of the staged queue
   void checkpoint_host() { h_ckpt = h_rows; }
   // true: the rows changed back, install them (nom_install)
   bool restore_host() {
@@ -3601,12 +3612,13 @@ static void bind_mode(ks_ctx* ctx, bool required) {
   cores_mode(ctx);
 }
 
-int ks_stage_pods(ks_ctx* ctx, const ks_pod_cols* pods, int32_t p) {
-  if (!ctx || !pods || p < 0) return ctx ? (ctx->err = "ks_stage_pods: bad args", KS_EINVAL) : KS_EINVAL;
-  if (!ctx->nodes.blob.get()) KS_FAIL(ctx, KS_ESTATE, "ks_stage_pods before ks_load_nodes");
-  KS_NOM_REFUSE(ctx, "ks_stage_pods / ks_schedule");
+// who != NULL: ks_stage_pods_nominated, the pods' nominations (validated by the caller)
+static int stage_pods_impl(ks_ctx* ctx, const ks_pod_cols* pods, int32_t p, const ks_nomination* who) {
+  const char* name = who ? "ks_stage_pods_nominated" : "ks_stage_pods";
+  if (!ctx->nodes.blob.get()) KS_FAIL(ctx, KS_ESTATE, "%s before ks_load_nodes", name);
+  if (!who) KS_NOM_REFUSE(ctx, "ks_stage_pods / ks_schedule");
   if (ctx->cfg.quota.enable && pods->quota && !ctx->quota.blob.get())
-    KS_FAIL(ctx, KS_ESTATE, "ElasticQuota enabled but ks_load_quotas not called");
+    KS_FAIL(ctx, KS_ESTATE, "%s: ElasticQuota enabled but ks_load_quotas not called", name);
   if (int rc = validate_pods(ctx, pods, p); rc != KS_OK) return rc;
   HIPCHK(ctx, hipSetDevice(ctx->device));
   if (ensure_stage(ctx, ctx->st, p) != KS_OK) return KS_ENOMEM;
@@ -3614,8 +3626,32 @@ int ks_stage_pods(ks_ctx* ctx, const ks_pod_cols* pods, int32_t p) {
   ctx->staged.np = p;
   ctx->staged.stale = false;
   ctx->staged.bind_required = ctx->staged.val_bind_required;
+  ctx->nom.q_staged = who != nullptr;
+  ctx->nom.q_who.assign(who, who + (who ? p : 0));
   HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
   return KS_OK;
+}
+
+int ks_stage_pods(ks_ctx* ctx, const ks_pod_cols* pods, int32_t p) {
+  if (!ctx || !pods || p < 0) return ctx ? (ctx->err = "ks_stage_pods: bad args", KS_EINVAL) : KS_EINVAL;
+  return stage_pods_impl(ctx, pods, p, nullptr);
+}
+
+int ks_stage_pods_nominated(ks_ctx* ctx, const ks_pod_cols* pods, int32_t p, const ks_nomination* who) {
+  if (!ctx || !pods || p < 0 || (p > 0 && !who))
+    return ctx ? (ctx->err = "ks_stage_pods_nominated: bad args", KS_EINVAL) : KS_EINVAL;
+  if (!ctx->nodes.blob.get()) KS_FAIL(ctx, KS_ESTATE, "ks_stage_pods_nominated before ks_load_nodes");
+  std::unordered_set<int64_t> seen;
+  for (int32_t i = 0; i < p; ++i) {
+    if (who[i].nominated_node < -1 || who[i].nominated_node >= ctx->nodes.n)
+      KS_FAIL(ctx, KS_EINVAL, "ks_stage_pods_nominated: pod %d: nominated node %d outside [-1, %lld)", i,
+              who[i].nominated_node, (long long)ctx->nodes.n);
+    if (who[i].self_id < -1) KS_FAIL(ctx, KS_EINVAL, "ks_stage_pods_nominated: pod %d: self_id %lld below -1", i, (long long)who[i].self_id);
+    if (who[i].self_id >= 0 && !seen.insert(who[i].self_id).second)
+      KS_FAIL(ctx, KS_EINVAL, "ks_stage_pods_nominated: self_id %lld appears twice in the queue", (long long)who[i].self_id);
+  }
+  static const ks_nomination none{0, -1, -1};
+  return stage_pods_impl(ctx, pods, p, p > 0 ? who : &none);
 }
 
 static hipEvent_t take_event(ks_ctx* ctx, size_t i) {
@@ -3715,6 +3751,7 @@ static CommitArgs commit_args(ks_ctx* ctx, PodStage& st, int32_t total, int32_t 
   ca.topo_count = ctx->topo.count;
   ca.topo_npad = ctx->nodes.npad;
   ca.topo_best = ctx->topo.scr ? &ctx->topo.scr->best_total : nullptr;
+  ca.nomq = nullptr;
   return ca;
 }
 
@@ -4121,6 +4158,102 @@ static int topo_step(ks_ctx* ctx) {
   return cores_pass_refresh(ctx);
 }
 
+// the device table's row order (nom_install): by node, a node's rows in descending priority, equal ones in caller order
+static std::vector<int32_t> nom_order(const std::vector<NomRow>& rows) {
+  std::vector<int32_t> order(rows.size());
+  for (size_t i = 0; i < rows.size(); ++i) order[i] = (int32_t)i;
+  std::stable_sort(order.begin(), order.end(), [&](int32_t x, int32_t y) {
+    if (rows[x].node != rows[y].node) return rows[x].node < rows[y].node;
+    return rows[x].prio > rows[y].prio;
+  });
+  return order;
+}
+
+// The queue table of one schedule call (ks_nominated.h): the rows' request words and count with their per-node prefix
+// sums, and the staged pods' nominations resolved against the table as it is now.
+static int nom_queue_build(ks_ctx* ctx) {
+  NomTable& nt = ctx->nom;
+  const auto& rows = nt.h_rows;
+  const size_t m = rows.size(), np = (size_t)ctx->staged.np;
+  const std::vector<int32_t> order = nom_order(rows);
+  size_t off = 0;
+  auto take = [&](size_t bytes) { const size_t o = off; off = align16(off + bytes); return o; };
+  const size_t o_val = take(m * 8 * kNomCols), o_pre = take(m * 8 * kNomCols), o_node = take(m * 4),
+               o_pods = take(np * sizeof(NomPod)), o_prev = take(16), o_q = take(sizeof(DevNomQueue));
+  std::vector<unsigned char> h(off, 0);
+  int64_t* val = (int64_t*)(h.data() + o_val);
+  int64_t* pre = (int64_t*)(h.data() + o_pre);
+  int32_t* rnode = (int32_t*)(h.data() + o_node);
+  NomPod* pods = (NomPod*)(h.data() + o_pods);
+  std::unordered_map<int64_t, int32_t> pos_of;
+  for (size_t pos = 0; pos < m; ++pos) {
+    const NomRow& r = rows[(size_t)order[pos]];
+    const bool first = pos == 0 || rows[(size_t)order[pos - 1]].node != r.node;
+    for (int d = 0; d < kNomCols; ++d) {
+      const int64_t v = d < kNomWords ? r.req[d] : 1;
+      val[(size_t)d * m + pos] = v;
+      pre[(size_t)d * m + pos] = v + (first ? 0 : pre[(size_t)d * m + pos - 1]);
+    }
+    rnode[pos] = r.node;
+    pos_of.emplace(r.id, (int32_t)pos);
+  }
+  nt.q_owners = 0;
+  for (size_t i = 0; i < np; ++i) {
+    const ks_nomination& w = nt.q_who[i];
+    NomPod& d = pods[i];
+    d.prio = w.priority;
+    d.only = w.nominated_node;
+    d.own = -1;
+    if (w.self_id >= 0)
+      if (auto it = pos_of.find(w.self_id); it != pos_of.end()) d.own = it->second;
+    d.owner = (w.self_id >= 0 || w.nominated_node >= 0) ? 1 : 0;
+    nt.q_owners += d.owner;
+  }
+  if (dev_alloc(ctx, nt.qblob, off) != KS_OK) return KS_ENOMEM;
+  unsigned char* b = (unsigned char*)nt.qblob.get();
+  DevNomQueue& q = nt.q;
+  q.beg = nt.nomt.beg;
+  q.prio = nt.nomt.prio;
+  q.val = (int64_t*)(b + o_val);
+  q.pre = (int64_t*)(b + o_pre);
+  q.row_node = (const int32_t*)(b + o_node);
+  q.pods = (const NomPod*)(b + o_pods);
+  q.prev = (int32_t*)(b + o_prev);
+  q.m = (int64_t)m;
+  q.n = ctx->nodes.n;
+  memcpy(h.data() + o_q, &q, sizeof(q));
+  nt.dq = (DevNomQueue*)(b + o_q);
+  HIPCHK(ctx, hipMemcpyAsync(b, h.data(), off, hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));  // (h leaves scope)
+  return KS_OK;
+}
+
+static int nom_install(ks_ctx* ctx);
+
+// After a schedule call with the table: the rows of the owners that were scheduled leave the host mirror, and the
+// device table is rebuilt from it (upstream assume -> DeleteNominatedPodIfExists).
+static int nom_queue_finish(ks_ctx* ctx) {
+  NomTable& nt = ctx->nom;
+  std::vector<int32_t> idx;
+  for (int32_t i = 0; i < ctx->staged.np; ++i)
+    if (nt.q_who[(size_t)i].self_id >= 0) idx.push_back(i);
+  if (idx.empty()) return KS_OK;
+  // (owners are few: one small read each, then one wait)
+  std::vector<ks_result> res(idx.size());
+  for (size_t k = 0; k < idx.size(); ++k)
+    HIPCHK(ctx, hipMemcpyAsync(&res[k], ctx->st.results + idx[k], sizeof(ks_result), hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+  std::unordered_set<int64_t> gone;
+  for (size_t k = 0; k < idx.size(); ++k)
+    if (res[k].status == KS_S_SCHEDULED) gone.insert(nt.q_who[(size_t)idx[k]].self_id);
+  if (gone.empty()) return KS_OK;
+  const size_t before = nt.h_rows.size();
+  nt.h_rows.erase(std::remove_if(nt.h_rows.begin(), nt.h_rows.end(), [&](const NomRow& r) { return gone.count(r.id) != 0; }),
+                  nt.h_rows.end());
+  if (nt.h_rows.size() == before) return KS_OK;
+  return nom_install(ctx);
+}
+
 template <int NSC>
 static int launch_pass(ks_ctx* ctx, int32_t ppw, int sweep_blocks, const PipeShape* pipe,
                        std::vector<std::pair<int, size_t>>* evs, size_t* evn) {
@@ -4177,6 +4310,7 @@ static int launch_pass(ks_ctx* ctx, int32_t ppw, int sweep_blocks, const PipeSha
   sa.list_bound = nullptr;
   sa.list_top = nullptr;
   sa.list_k = 0;
+  sa.nomq = ctx->nom.q_on ? ctx->nom.dq : nullptr;
   const int feat = kernel_feat(ctx);
   sa.dv = ctx->ddv.get();
   sa.nv = ctx->dnv.get();
@@ -4195,7 +4329,7 @@ static int launch_pass(ks_ctx* ctx, int32_t ppw, int sweep_blocks, const PipeSha
       const int32_t sh = ctx->rank * ctx->vshards + v;
       sa.c0 = shard_lo(sh);
       sa.c1 = shard_lo(sh + 1);
-      le = pl.sweep(blocks, st, sa);
+      le = ctx->nom.q_on ? pl.sweep_nom(blocks, st, sa) : pl.sweep(blocks, st, sa);
     }
   };
   // patched: commit k-2 wrote this pass's first pod and its rows are final
@@ -4338,7 +4472,16 @@ static int launch_pass(ks_ctx* ctx, int32_t ppw, int sweep_blocks, const PipeSha
   rec(2, cs);
   if (ca.pre_rsv) HIPCHK(ctx, pl.reserve_pre(ctx->batch, cs, ca));  // (timed with the commit)
   // (the dedicated fq kernel does not run the patched pipeline's passes, ks_plan.h)
-  if (plan.mono) HIPCHK(ctx, pl.commit_mono(plan.qcache, plan.mono_smem, cs, ca));
+  if (ctx->nom.q_on) {
+    // a nominated table: the general commit's NOM variant only, then the retire step when the queue has owners
+    ca.nomq = ctx->nom.dq;
+    HIPCHK(ctx, pl.commit_nom(plan.qcache, plan.smem, cs, ca));
+    if (ctx->nom.q_owners > 0) {
+      hipLaunchKernelGGL((nom_retire_kernel<>), dim3(1), dim3(64), 0, cs, ctx->nom.q, (const ks_result*)ctx->st.results,
+                         (const int32_t*)ctx->cursor.get(), ctx->counters.get());
+      HIPCHK(ctx, hipGetLastError());
+    }
+  } else if (plan.mono) HIPCHK(ctx, pl.commit_mono(plan.qcache, plan.mono_smem, cs, ca));
   else if (plan.fq && !patch) HIPCHK(ctx, fq_launcher(ctx->nodes.nsc).commit(plan.fq_keys, plan.fq_smem, cs, ca));
   else HIPCHK(ctx, pl.commit(plan.qcache, plan.smem, cs, ca));
   rec(2, cs);
@@ -4350,9 +4493,19 @@ static int launch_pass(ks_ctx* ctx, int32_t ppw, int sweep_blocks, const PipeSha
 
 static int schedule_staged_impl(ks_ctx* ctx) {
   if (!ctx->nodes.blob.get()) KS_FAIL(ctx, KS_ESTATE, "schedule before ks_load_nodes");
-  KS_NOM_REFUSE(ctx, "ks_schedule_staged");
+  if (!ctx->nom.q_staged) KS_NOM_REFUSE(ctx, "ks_schedule_staged");
   if (ctx->staged.stale)
     KS_FAIL(ctx, KS_ESTATE, "ks_schedule_staged: the staged batch predates a table reload; call ks_stage_pods again");
+  // a non-empty nominated table under a batch staged with nominations: the NOM variants (ks_nominated.h), one shard,
+  // not pipelined
+  ctx->nom.q_on = false;
+  if (ctx->nom.q_staged && !ctx->nom.h_rows.empty()) {
+    if (ctx->nranks * ctx->vshards > 1 || ctx->comm || ctx->loop)
+      KS_FAIL(ctx, KS_EUNSUPPORTED, "ks_schedule_staged: a nominated table is loaded (%zu pods) and the nodes are sharded "
+                                    "(ks_shard_init): the queue with a table runs on one shard only",
+              ctx->nom.h_rows.size());
+    ctx->nom.q_on = true;
+  }
   HIPCHK(ctx, hipSetDevice(ctx->device));
   bind_mode(ctx, ctx->staged.bind_required);
   ctx->staged.cpusets_clobbered = false;
@@ -4362,6 +4515,14 @@ static int schedule_staged_impl(ks_ctx* ctx) {
   {
     if (int rc = commit_attr_set(ctx); rc != KS_OK) return rc;
     hipError_t e = hipSuccess;
+    if (ctx->nom.q_on) {
+      const PassLaunch npl = pass_launcher(ctx->plan.feat, ctx->nodes.nsc, ctx->plan.wide);
+      if (!npl.commit_nom || ctx->cfg.topology.enable)  // (unreachable: ks_load_nominated admits no such plugin set)
+        KS_FAIL(ctx, KS_EUNSUPPORTED, "ks_schedule_staged: a nominated table with a plugin set it is not modelled with");
+      e = npl.commit_nom_attr(ctx->plan.qcache, ctx->plan.smem);
+      if (e != hipSuccess) KS_FAIL(ctx, KS_EHIP, "hipFuncSetAttribute(commit LDS %zu): %s", ctx->plan.smem, hipGetErrorString(e));
+      if (int rc = nom_queue_build(ctx); rc != KS_OK) return rc;
+    }
     const size_t sel_smem = select_smem(ctx->nodes.nchunks);
     if (sel_smem > kLdsBytes) KS_FAIL(ctx, KS_EUNSUPPORTED, "too many nodes for the select kernel's LDS (%lld nodes)", (long long)ctx->nodes.n);
     e = hipFuncSetAttribute((const void*)select_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sel_smem);
@@ -4407,7 +4568,7 @@ static int schedule_staged_impl(ks_ctx* ctx) {
   // pipelined passes: pass 0 sweeps from pod 0, no commit has written rows yet
   PipeShape pshape{};
   const PipeShape* pipe = nullptr;
-  if (pipelined(ctx)) {
+  if (!ctx->nom.q_on && pipelined(ctx)) {
     if (ensure_pipe(ctx) != KS_OK) return KS_EHIP;
     static const int64_t env_patch = env_i64("KS_PIPE_PATCH", 1, 0, 1);
     pshape.patch = env_patch != 0 && ctx->kc.monotone;
@@ -4478,7 +4639,8 @@ static int schedule_staged_impl(ks_ctx* ctx) {
   } graph_guard{gexec};
   while (host_cursor < np) {
     const int32_t remaining = np - host_cursor;
-    const int32_t g = std::min<int32_t>((remaining + ctx->batch - 1) / ctx->batch, 256);
+    // (with a nominated table every owner pod is a pass of its own)
+    const int32_t g = std::min<int32_t>((remaining + ctx->batch - 1) / ctx->batch + (ctx->nom.q_on ? std::min(ctx->nom.q_owners, remaining) : 0), 256);
     for (int32_t i = 0; i < g; i += gexec ? kGraphIters : 1) {
       if (gexec) {
         HIPCHK(ctx, hipGraphLaunch(gexec, ctx->stream));
@@ -4516,10 +4678,14 @@ static int schedule_staged_impl(ks_ctx* ctx) {
   ctx->stats.pre_reserves = (int64_t)cnt[5];
   ctx->stats.pipelined = pipe ? (pipe->patch ? 2 : 1) : 0;
   const CommitPlan& plan = ctx->plan;
-  const bool keys = !plan.mono && plan.fq_keys && !(pipe && pipe->patch);
+  const bool keys = !ctx->nom.q_on && !plan.mono && plan.fq_keys && !(pipe && pipe->patch);
   ctx->stats.commit_lds_bytes = (int64_t)(keys ? plan.fq_smem : plan.smem);
   ctx->stats.commit_helpers = keys ? 2 : (plan.hint ? 1 : 0);
   for (int i = 0; i < 8; ++i) ctx->stats.diag[i] = (int64_t)cnt[8 + i];
+  if (ctx->nom.q_on) {
+    ctx->nom.q_on = false;
+    if (int rc = nom_queue_finish(ctx); rc != KS_OK) return rc;
+  }
   for (size_t i = 0; i + 1 < evs.size(); i += 2) {
     float e = 0;
     (void)hipEventElapsedTime(&e, ctx->ev_pool[evs[i].second], ctx->ev_pool[evs[i + 1].second]);
@@ -4563,6 +4729,14 @@ int ks_schedule(ks_ctx* ctx, const ks_pod_cols* pods, int32_t p, ks_result* out)
   return ks_fetch_results(ctx, out, p);
 }
 
+int ks_schedule_nominated(ks_ctx* ctx, const ks_pod_cols* pods, int32_t p, const ks_nomination* who, ks_result* out) {
+  int rc = ks_stage_pods_nominated(ctx, pods, p, who);
+  if (rc != KS_OK) return rc;
+  rc = ks_schedule_staged(ctx);
+  if (rc != KS_OK) return rc;
+  return ks_fetch_results(ctx, out, p);
+}
+
 // ---- nominated pods (ks_nominated.h) ----
 
 // The device table from ctx->nom.h_rows: CSR by node, a node's entries in descending priority (equal priorities in caller
@@ -4575,13 +4749,8 @@ static int nom_install(ks_ctx* ctx) {
   ctx->nom.fit = nullptr;
   const size_t m = ctx->nom.h_rows.size(), n = (size_t)ctx->nodes.n;
   if (m == 0) return KS_OK;
-  std::vector<int32_t> order(m);
-  for (size_t i = 0; i < m; ++i) order[i] = (int32_t)i;
   const auto& rows = ctx->nom.h_rows;
-  std::stable_sort(order.begin(), order.end(), [&](int32_t x, int32_t y) {
-    if (rows[x].node != rows[y].node) return rows[x].node < rows[y].node;
-    return rows[x].prio > rows[y].prio;
-  });
+  const std::vector<int32_t> order = nom_order(rows);
   std::vector<int64_t> beg(n + 1, 0);
   std::vector<int32_t> nodes;
   for (size_t i = 0; i < m; ++i) ++beg[(size_t)rows[i].node + 1];

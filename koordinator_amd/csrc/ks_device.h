@@ -512,6 +512,7 @@ template <int NSC, bool DEBUG>
 __device__ __forceinline__ EvalOut eval_pod_node(const Cfg& c, const PodRec& p, const NodeReg<NSC>& r) {
   EvalOut o;
   uint32_t rs = 0;
+  // (NodeResourcesFit: nom_fit_fails in ks_nominated.h runs the same checks with a nominated sum added; keep in step)
   if (c.fit_filter) {
     if (DEBUG) {
       if (r.pods_full) rs |= KS_R_FIT_PODS;

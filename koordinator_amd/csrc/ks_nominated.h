@@ -106,4 +106,117 @@ __global__ __launch_bounds__(256) void nominated_overlay_kernel(DevNominated t, 
   if (lane == 0) fit_bits[node] = o.reasons & kNomFitBits;
 }
 
+// ---- the batched queue with a table loaded (ks_schedule_nominated, DESIGN §2.12a "queue") ----
+//
+//   queue table              built from the host rows at every schedule call, next to the CSR above: per row the seven
+//                            request words and a count word (1; 0 once retired) as columns `val`, and their inclusive
+//                            prefix sums within the node as columns `pre`.  A node's rows are in descending priority, so
+//                            the counted sum for a pod is "binary-search the last row with priority >= the pod's, read
+//                            one prefix"; the pod's own row, when it lies inside that range, is subtracted.
+//   NomPod                   per staged pod: priority, own nominated node, the index of its own row, owner flag.  An
+//                            owner (self_id >= 0 or nominated_node >= 0) is scheduled alone: the commit's pass ends in
+//                            front of it, and a pass that starts at it takes that pod only (ks_pass.h, NOM variants).
+//   nom_fit_fails            per lane (lane = node): NodeResourcesFit on the node row plus the counted sum.
+//   nom_retire_kernel        one wave after each commit: when the pass was an owner's and it reserved, the owner's row is
+//                            zeroed and its node's prefix sums rebuilt (lane = column), so no later pod counts it.
+constexpr int kNomCols = kNomWords + 1;  // the request words, then the count
+
+struct NomPod {
+  int32_t prio;
+  int32_t only;   // the pod's own nominated node, tried first (-1 = none)
+  int32_t own;    // its own row in the table (-1 = none)
+  int32_t owner;  // 1: scheduled alone
+};
+
+struct DevNomQueue {
+  const int64_t* beg;       // [n + 1], DevNominated's
+  const int32_t* prio;      // [m]
+  int64_t* val;             // [kNomCols][m]
+  int64_t* pre;             // [kNomCols][m]
+  const int32_t* row_node;  // [m]
+  const NomPod* pods;       // [staged pods]
+  int32_t* prev;            // the cursor before the last commit (nom_retire_kernel)
+  int64_t m, n;
+};
+
+__device__ __forceinline__ NomPod load_nompod_uniform(const NomPod* p) {
+  NomPod r;
+#if defined(__HIP_DEVICE_COMPILE__)
+  typedef const __attribute__((address_space(4))) int64_t* ConstWords;
+  const ConstWords src = (ConstWords)p;
+  int64_t* dst = reinterpret_cast<int64_t*>(&r);
+  dst[0] = src[0];
+  dst[1] = src[1];
+#else
+  r = *p;
+#endif
+  return r;
+}
+
+// NodeResourcesFit of pod p (nomination w) on node row r with the counted rows of [b, e) added: true = it fails.
+// The caller has tested b != e.  Divergent across lanes (each lane its own node), no cross-lane traffic.
+// The checks are those of eval_pod_node's Fit (ks_device.h, DEBUG = false) on the row with the sum applied as
+// nominated_overlay_kernel applies it; they are written out here on the sum's words so that the node row -- whose score
+// terms must stay without the nominated pods -- is not copied per pod in the sweep's loop.  Keep the two in step.
+template <int NSC>
+__device__ __forceinline__ bool nom_fit_fails(const DevNomQueue& q, const Cfg& c, const NomPod& w, const PodRec& p,
+                                              const NodeReg<NSC>& r, int64_t b, int64_t e) {
+  if (!c.fit_filter) return false;
+  int64_t lo = b, hi = e;  // -> the first row below the pod's priority
+  while (lo < hi) {
+    const int64_t mid = (lo + hi) >> 1;
+    if (gld(q.prio + mid) >= w.prio) lo = mid + 1;
+    else hi = mid;
+  }
+  if (lo == b) return false;
+  const int64_t last = lo - 1;
+  const bool own = (int64_t)w.own >= b && (int64_t)w.own <= last;
+  auto sum = [&](int d) -> int64_t {
+    int64_t s = gld(q.pre + (int64_t)d * q.m + last);
+    if (own) s -= gld(q.val + (int64_t)d * q.m + w.own);
+    return s;
+  };
+  const int64_t cnt = sum(kNomWords);
+  if (cnt == 0) return false;
+  bool bad = (int64_t)r.pod_count + cnt + 1 > (int64_t)r.allowed;
+  if (!(p.flags & kPodAllZero)) {
+    bad |= p.cpu > r.free_cpu - sum(0);
+    bad |= p.mem > r.free_mem - sum(1);
+    bad |= p.eph > r.free_eph - sum(2);
+#pragma unroll
+    for (int k = 0; k < NSC; ++k)
+      if (p.sc[k] != 0) bad |= p.sc[k] > r.free_sc[k] - sum(3 + k);
+  }
+  return bad;
+}
+
+// counters: [12] owner passes (ks_stats.diag[4]), [13] retired rows (ks_stats.diag[5])
+// (a template so that the header's includers that never launch it define nothing)
+template <int NCOLS = kNomCols>
+__global__ __launch_bounds__(64) void nom_retire_kernel(DevNomQueue q, const ks_result* __restrict__ results,
+                                                        const int32_t* __restrict__ cursor, unsigned long long* counters) {
+  const int lane = threadIdx.x;
+  const int32_t c0 = __builtin_amdgcn_readfirstlane(*q.prev), c1 = __builtin_amdgcn_readfirstlane(*cursor);
+  if (c1 <= c0) return;  // the pass committed nothing
+  if (lane == 0) *q.prev = c1;
+  const NomPod w = load_nompod_uniform(q.pods + c0);
+  if (!w.owner) return;
+  if (lane == 0) atomicAdd(&counters[12], 1ull);
+  if (w.own < 0 || w.own >= q.m || __builtin_amdgcn_readfirstlane(results[c0].status) != KS_S_SCHEDULED) return;
+  const int64_t node = gld(q.row_node + w.own);
+  if (node < 0 || node >= q.n) return;
+  const int64_t b = gld(q.beg + node), e = gld(q.beg + node + 1);
+  if (lane < NCOLS) {
+    int64_t* v = q.val + (int64_t)lane * q.m;
+    int64_t* pf = q.pre + (int64_t)lane * q.m;
+    gst(v + w.own, (int64_t)0);
+    int64_t run = 0;
+    for (int64_t i = b; i < e; ++i) {
+      run += i == w.own ? 0 : gld(v + i);
+      gst(pf + i, run);
+    }
+  }
+  if (lane == 0) atomicAdd(&counters[13], 1ull);
+}
+
 }  // namespace ks

@@ -14,6 +14,7 @@
 #include "ks_cpuset.h"
 #include "ks_numa.h"
 #include "ks_topo.h"
+#include "ks_nominated.h"
 
 namespace ks {
 
@@ -67,6 +68,8 @@ struct SweepArgs {
   const uint64_t* list_bound;
   unsigned long long* list_top;
   int32_t list_k;
+  // the NOM variant only (a nominated table is loaded, ks_nominated.h): the queue table and the pods' nominations
+  const DevNomQueue* nomq;
 };
 
 // local key: ((total+1) << 6) | (63 - lane); 0 = no feasible node.  Max = best score, lowest lane.
@@ -76,8 +79,11 @@ struct SweepArgs {
 #ifndef KS_SWEEP_WAVES
 #define KS_SWEEP_WAVES 4  // (profiles/r03_sweep_w4_ab.txt: C5 sweep 51.1 -> 43.1 us per launch)
 #endif
-template <int NSC, int FEAT, int NW = kNumaDev>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((FEAT == 0 && NSC <= 2) ? KS_SWEEP_WAVES : 1)))
+// NOM (ks_nominated.h, a context with a nominated table; never the instantiation a context without one launches): a node
+// with live rows fails a pod's Fit when it fails with the counted rows added, and a pod whose own nominated node passes
+// its Filters has that node alone (evaluateNominatedNode); scores are the node's own.
+template <int NSC, int FEAT, int NW = kNumaDev, bool NOM = false>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((FEAT == 0 && NSC <= 2 && !NOM) ? KS_SWEEP_WAVES : 1)))
 void sweep_kernel(SweepArgs a) {
   const int lane = threadIdx.x & 63;
   // wave-uniform work indices (readfirstlane: the compiler keeps the pod loop and its records scalar).
@@ -192,6 +198,14 @@ void sweep_kernel(SweepArgs a) {
           st_port = gld(d.host_ports + node);
         }
       }
+      int64_t nom_b = 0, nom_e = 0;  // NOM: the node's rows (none: one compare of two adjacent offsets)
+      if constexpr (NOM) {
+        if (node < a.n) {
+          const int64_t* beg = a.nomq->beg;
+          nom_b = gld(beg + node);
+          nom_e = gld(beg + node + 1);
+        }
+      }
       const int32_t p0 = g * a.ppw, p1 = min(np, p0 + a.ppw);
       uint32_t best = 0, second = 0;
       for (int32_t p = p0; p < p1; ++p) {
@@ -200,6 +214,29 @@ void sweep_kernel(SweepArgs a) {
             a.c, pod, r, [&](auto&& f) { return f(RsvG<false>(*a.rv, node)); },
             [&]() { return DevGView{*a.dv, node}; }, [&]() { return NumaGViewT<NW>{*a.nv, node}; });
         if ((FEAT & 4) && a.c.stat) stat_eval(a.c, load_stat_uniform(a.pstat + cursor + p), st_hard, st_soft, st_lab, st_port, o);
+        if constexpr (NOM) {
+          const DevNomQueue q = *a.nomq;
+          const NomPod w = load_nompod_uniform(q.pods + cursor + p);
+          if (nom_b != nom_e && nom_fit_fails<NSC>(q, a.c, w, pod, r, nom_b, nom_e)) o.reasons |= KS_R_FIT_PODS;
+          if (p == 0 && w.only >= 0 && w.only < a.n) {
+            // the pod's own nominated node first (wave-uniform).  Only for the pod at the cursor: an owner is
+            // committed only by the pass that starts at it, its keys in any other pass are never read.  Every lane
+            // evaluates that node, and when it passes no other node is feasible
+            const int64_t x = w.only;
+            const DevNodes d = *a.dn;
+            NodeReg<NSC> rx;
+            load_node<NSC>(a.c, d, x, 1, rx);
+            EvalOut ox = eval_full<NSC, false, true, FEAT>(
+                a.c, pod, rx, [&](auto&& f) { return f(RsvG<false>(*a.rv, x)); },
+                [&]() { return DevGView{*a.dv, x}; }, [&]() { return NumaGViewT<NW>{*a.nv, x}; });
+            if ((FEAT & 4) && a.c.stat)
+              stat_eval(a.c, load_stat_uniform(a.pstat + cursor + p), gld(d.taints_hard + x), gld(d.taints_soft + x),
+                        gld(d.labels + x), gld(d.host_ports + x), ox);
+            const int64_t xb = gld(q.beg + x), xe = gld(q.beg + x + 1);
+            if (xb != xe && nom_fit_fails<NSC>(q, a.c, w, pod, rx, xb, xe)) ox.reasons |= KS_R_FIT_PODS;
+            if (ox.reasons == 0 && node != x) o.reasons |= KS_R_FIT_PODS;
+          }
+        }
         if ((FEAT & 4) && a.phase == 0) {
           // normalization maxima over the feasible nodes, witness = lowest index holding each
           const uint64_t wit = 0xFFFFFFFFull - (uint64_t)node;
@@ -385,7 +422,24 @@ struct CommitArgs {
   int32_t* topo_count;       // [nprops][topo_npad]
   int64_t topo_npad;
   const long long* topo_best;  // mode 2: the topology step's total of the chosen node
+  // the NOM variant only (a nominated table is loaded, ks_nominated.h)
+  const DevNomQueue* nomq;
 };
+
+// NOM: the pods the pass commits -- an owner at the cursor alone, otherwise the pods in front of the first owner
+template <bool NOM>
+__device__ __forceinline__ int32_t nom_pass_pods(const CommitArgs& a, int32_t cursor0, int32_t np) {
+  if constexpr (NOM) {
+    const int lane = threadIdx.x & 63;
+    const NomPod* wp = a.nomq->pods;
+    const uint64_t own = __ballot(lane < np && gld(&wp[cursor0 + lane].owner) != 0);
+    if (own) {
+      const int32_t f = (int32_t)(__ffsll((long long)own) - 1);
+      return f == 0 ? 1 : f;
+    }
+  }
+  return np;
+}
 
 // One pod's NodeNUMAResource + DeviceShare Reserve on one node of its snapshot ranking, computed on the snapshot state
 // (what the commit's Reserve computes on the slot state of a node no earlier pod of the pass touched).
@@ -671,10 +725,14 @@ __device__ __forceinline__ Cands resolve_cands(const uint32_t* cand_chunk, const
 
 // Re-scan a candidate chunk's untouched nodes exactly for one pod (lane = node); touched nodes are
 // covered by the slot evaluation.
-template <int NSC, int FEAT, int NW>
+// NOM: the nominated nodes of the chunk are always among the untouched ones (a Reserve onto one ends the pass), so the
+// re-scan applies the table exactly as the sweep does -- a node that fails the pod's Fit with its counted rows added
+// stays out.  `qpod` is the pod's queue index.  (A pod with a nominated node of its own is the only pod of its pass
+// and nothing is touched in front of it, so the only-node rule never reaches a re-scan.)
+template <int NSC, int FEAT, int NW, bool NOM = false>
 __device__ __forceinline__ uint64_t rescan_untouched(const CommitArgs& a, const Cfg& cfg, const PodRec& pod,
                                                      int64_t chunk, uint64_t touched_mask, const NormM& M,
-                                                     const PodStat* ps) {
+                                                     const PodStat* ps, int32_t qpod = 0) {
   const int lane = threadIdx.x & 63;
   const int64_t node = chunk * 64 + lane;
   NodeReg<NSC> r;
@@ -693,6 +751,14 @@ __device__ __forceinline__ uint64_t rescan_untouched(const CommitArgs& a, const 
       cfg, pod, r, [&](auto&& f) { return f(RsvG<false>(*a.rv, node)); },
       [&]() { return DevGView{*a.dv, node}; }, [&]() { return NumaGViewT<NW>{*a.nv, node}; });
   if ((FEAT & 4) && cfg.stat) stat_eval(cfg, *ps, sh, ss, sl, sp, o);
+  if constexpr (NOM) {
+    if (node < a.n) {
+      const DevNomQueue q = *a.nomq;
+      const int64_t nb = gld(q.beg + node), ne = gld(q.beg + node + 1);
+      if (nb != ne && nom_fit_fails<NSC>(q, cfg, load_nompod_uniform(q.pods + qpod), pod, r, nb, ne))
+        o.reasons |= KS_R_FIT_PODS;
+    }
+  }
   const bool skip = o.reasons || ((touched_mask >> lane) & 1ull);
   return wave_max_u64(skip ? 0ull : gkey(key_total(cfg, o, M), node));
 }
@@ -748,7 +814,11 @@ __device__ __forceinline__ void lds_rawtop(int64_t* rawtop, const uint64_t* cand
   }
 }
 
-template <int NSC, bool QC, int FEAT, int NW = kNumaDev>
+// NOM (a context with a nominated table; never the instantiation a context without one launches): the slot rows know
+// nothing of the table, so the pass takes an owner pod alone, ends in front of the next one, and ends behind a Reserve
+// onto a node with live rows -- no touched slot is then ever re-evaluated where the table counts; the untouched nodes
+// a re-scan evaluates get the table applied as in the sweep (rescan_untouched<NOM>).
+template <int NSC, bool QC, int FEAT, int NW = kNumaDev, bool NOM = false>
 __global__ __launch_bounds__(commit_threads(FEAT)) void commit_kernel(CommitArgs a) {
   constexpr int NT = commit_threads(FEAT);
   constexpr bool RSV = (FEAT & 1) != 0;
@@ -825,7 +895,8 @@ __global__ __launch_bounds__(commit_threads(FEAT)) void commit_kernel(CommitArgs
     return;
   }
   if (pipe_bubble(a, cursor0)) return;
-  const int32_t np = topo_pass_pods(a, cursor0, min(a.batch, a.total_pods - cursor0));
+  const int32_t np_q = topo_pass_pods(a, cursor0, min(a.batch, a.total_pods - cursor0));
+  const int32_t np = nom_pass_pods<NOM>(a, cursor0, np_q);
   if (np == 0) return;  // a topology pod at the cursor: the next topology step takes it
 #ifdef KS_COMMIT_STAMPS
   uint64_t ph[8] = {0, 0, 0, 0, 0, 0, 0, 0};
@@ -1208,6 +1279,7 @@ __global__ __launch_bounds__(commit_threads(FEAT)) void commit_kernel(CommitArgs
   tcat = __builtin_amdgcn_s_memtime();
 #endif
 
+  [[maybe_unused]] bool nom_cut = false;  // NOM: this pod reserved onto a node with live rows
   for (int32_t j = 0; j < np; ++j) {
     const uint32_t st = st_next;
     const Cands cj = cn;
@@ -1416,7 +1488,7 @@ __global__ __launch_bounds__(commit_threads(FEAT)) void commit_kernel(CommitArgs
         const uint64_t kmax = wave_max_u64(((need >> lane) & 1ull) ? cj.ub : 0ull);
         const int sel = __ffsll((long long)__ballot(((need >> lane) & 1ull) && cj.ub == kmax)) - 1;
         const int64_t c = (int64_t)(uint32_t)__shfl((int)cj.chunk, sel, 64);
-        const uint64_t v = rescan_untouched<NSC, FEAT, NW>(a, cfg, pod, c, touched[c], Muse, &pst);
+        const uint64_t v = rescan_untouched<NSC, FEAT, NW, NOM>(a, cfg, pod, c, touched[c], Muse, &pst, cursor0 + j);
         ++rescans;
         best = umax64(best, v);
         need &= ~(1ull << sel);
@@ -1439,6 +1511,13 @@ __global__ __launch_bounds__(commit_threads(FEAT)) void commit_kernel(CommitArgs
     }
     const int32_t node = (int32_t)gkey_node(best);
     const int64_t score = gkey_score(best);
+    if constexpr (NOM) {
+      // live rows: the node's prefix count at its last row (a node whose rows were all retired in this call is a
+      // node like any other again)
+      const DevNomQueue q = *a.nomq;
+      const int64_t nb = gld(q.beg + node), ne = gld(q.beg + node + 1);
+      nom_cut = nb != ne && gld(q.pre + (int64_t)kNomWords * q.m + ne - 1) != 0;
+    }
     const uint32_t pflags = __builtin_amdgcn_readlane(my_flags, j);
     const int64_t* podw = reinterpret_cast<const int64_t*>(&spods[j]);
     // ---- Reserve: NodeInfo.AddPod + podAssignCache.assign on the slot row (lane = term) ----
@@ -1960,6 +2039,12 @@ __global__ __launch_bounds__(commit_threads(FEAT)) void commit_kernel(CommitArgs
     KS_STAMP(5);
     }
   next_pod:
+    if constexpr (NOM) {
+      if (nom_cut) {
+        processed = j + 1;  // the slot row of a node with live rows is never re-evaluated
+        break;
+      }
+    }
     if (j + 1 < np) lookahead(j + 1);
     KS_STAMP(1);
 #ifdef KS_COMMIT_CAT
@@ -2021,7 +2106,7 @@ __global__ __launch_bounds__(commit_threads(FEAT)) void commit_kernel(CommitArgs
     *a.cursor = cursor0 + processed;
     pipe_next(a, cursor0 + processed);
     atomicAdd(&a.counters[0], 1ull);
-    if (processed < np) atomicAdd(&a.counters[1], 1ull);
+    if (processed < np || (NOM && np < np_q)) atomicAdd(&a.counters[1], 1ull);
     atomicAdd(&a.counters[2], (unsigned long long)rescans);
     atomicAdd(&a.counters[3], (unsigned long long)misses);
     atomicAdd(&a.counters[15], (unsigned long long)fast);  // ks_stats.diag[7]: monotone fast picks
@@ -2164,6 +2249,11 @@ struct PassLaunch {
   hipError_t (*commit_mono_attr)(bool qc, size_t smem);
   // NUMA topology policy variants only (else null): reserve_pre_kernel, one workgroup per pod of the pass
   hipError_t (*reserve_pre)(int blocks, hipStream_t s, const CommitArgs& a);
+  // FEAT 0 and 4 at NUMA width 4 only (else null): the NOM variants of the sweep and the general commit, for a context
+  // with a nominated table (ks_nominated.h)
+  hipError_t (*sweep_nom)(int blocks, hipStream_t s, const SweepArgs& a);
+  hipError_t (*commit_nom)(bool qc, size_t smem, hipStream_t s, const CommitArgs& a);
+  hipError_t (*commit_nom_attr)(bool qc, size_t smem);
 };
 // The built FEAT variants, ascending (the Makefile's FEATS builds the same set: a mismatch is a link error), and those
 // built a second time at NUMA width 8 (ks_variant.hip with -DKS_NW=8, the Makefile's WFEATS).  The declarations

@@ -46,6 +46,30 @@ hipError_t commit_attr(bool qc, size_t smem) {
   return hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
 }
 
+#if (KS_FEAT == 0 || KS_FEAT == 4) && KS_NW == 4
+// the plugin sets a nominated table may be loaded with: the NOM variants (ks_nominated.h)
+#define KS_HAS_NOM 1
+hipError_t sweep_nom(int blocks, hipStream_t s, const SweepArgs& a) {
+  hipLaunchKernelGGL((sweep_kernel<NSC, F, NW, true>), dim3(blocks), dim3(256), 0, s, a);
+  return hipGetLastError();
+}
+
+hipError_t commit_nom(bool qc, size_t smem, hipStream_t s, const CommitArgs& a) {
+  if (qc) hipLaunchKernelGGL((commit_kernel<NSC, true, F, NW, true>), dim3(1), dim3(commit_threads(F)), smem, s, a);
+  else hipLaunchKernelGGL((commit_kernel<NSC, false, F, NW, true>), dim3(1), dim3(commit_threads(F)), smem, s, a);
+  return hipGetLastError();
+}
+
+hipError_t commit_nom_attr(bool qc, size_t smem) {
+  const void* fn = qc ? (const void*)commit_kernel<NSC, true, F, NW, true> : (const void*)commit_kernel<NSC, false, F, NW, true>;
+  return hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
+}
+#else
+constexpr auto sweep_nom = nullptr;
+constexpr auto commit_nom = nullptr;
+constexpr auto commit_nom_attr = nullptr;
+#endif
+
 #if KS_FEAT == 0
 // the monotone Fit + LoadAware [+ ElasticQuota] commit (ks_mono.h)
 hipError_t commit_mono(bool qc, size_t smem, hipStream_t s, const CommitArgs& a) {
@@ -87,11 +111,11 @@ PassLaunch KS_CAT(KS_CAT(KS_CAT(KS_CAT(pass_launch_f, KS_FEAT), _n), KS_NSC), _w
 PassLaunch KS_CAT(KS_CAT(KS_CAT(pass_launch_f, KS_FEAT), _n), KS_NSC)() {
 #endif
 #if KS_FEAT == 0
-  return PassLaunch{sweep, commit, commit_attr, commit_mono, commit_mono_attr, nullptr};
+  return PassLaunch{sweep, commit, commit_attr, commit_mono, commit_mono_attr, nullptr, sweep_nom, commit_nom, commit_nom_attr};
 #elif (KS_FEAT & 8) != 0
-  return PassLaunch{sweep, commit, commit_attr, nullptr, nullptr, reserve_pre};
+  return PassLaunch{sweep, commit, commit_attr, nullptr, nullptr, reserve_pre, sweep_nom, commit_nom, commit_nom_attr};
 #else
-  return PassLaunch{sweep, commit, commit_attr, nullptr, nullptr, nullptr};
+  return PassLaunch{sweep, commit, commit_attr, nullptr, nullptr, nullptr, sweep_nom, commit_nom, commit_nom_attr};
 #endif
 }
 

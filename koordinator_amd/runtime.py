@@ -111,6 +111,9 @@ def lib() -> C.CDLL:
     L.ks_eval_pod_summary_nominated.argtypes = [vp, C.POINTER(abi.KsPodCols), C.POINTER(abi.KsNomination), C.c_uint32,
                                                 C.c_int32, C.POINTER(abi.KsPodSummary), abi.P32, abi.P64, abi.P64,
                                                 abi.PU64, abi.PU64]
+    L.ks_stage_pods_nominated.argtypes = [vp, C.POINTER(abi.KsPodCols), C.c_int32, C.POINTER(abi.KsNomination)]
+    L.ks_schedule_nominated.argtypes = [vp, C.POINTER(abi.KsPodCols), C.c_int32, C.POINTER(abi.KsNomination),
+                                        C.POINTER(abi.KsResult)]
     L.ks_preempt_nominated.argtypes = [vp, C.POINTER(abi.KsPodCols), C.c_int32, C.c_uint32, C.c_int32, C.c_int64,
                                        C.POINTER(C.c_uint8), C.POINTER(abi.KsPreemptResult), abi.P32, C.c_int32,
                                        C.POINTER(C.c_uint8)]
@@ -380,6 +383,39 @@ class Evaluator:
         return {"node": out["node"].copy(), "status": out["status"].copy(), "score": out["score"].copy(),
                 "reservation": out["reservation"].copy(), "gpu_minors": out["gpu_minors"].copy(),
                 "rdma_minors": out["rdma_minors"].copy()}
+
+    @staticmethod
+    def _who_array(n: int, priority, nominated_node=None, self_id=None):
+        """[n] ks_nomination from three arrays of length n (None: no nominated node / no own row)"""
+        pr = np.asarray(priority, np.int64).reshape(-1)
+        nn = np.full(n, -1, np.int64) if nominated_node is None else np.asarray(nominated_node, np.int64).reshape(-1)
+        si = np.full(n, -1, np.int64) if self_id is None else np.asarray(self_id, np.int64).reshape(-1)
+        if not (pr.size == nn.size == si.size == n):
+            raise ValueError("priority, nominated_node and self_id must have one entry per pod")
+        who = (abi.KsNomination * max(n, 1))()
+        for i in range(n):
+            who[i] = abi.KsNomination(priority=int(pr[i]), nominated_node=int(nn[i]), self_id=int(si[i]))
+        return who
+
+    def schedule_nominated(self, pods: PodTable, priority, nominated_node=None, self_id=None) -> dict:
+        """schedule() with a nominated table loaded (ks_schedule_nominated): per pod its priority, its own nominated
+        node (-1 = none) and its own table id (-1 = none); the rows of the owners it schedules leave the table"""
+        who = self._who_array(pods.n, priority, nominated_node, self_id)
+        out = np.zeros(max(pods.n, 1), RESULT_DTYPE)
+        cols = pods.ks()
+        self._chk(self.L.ks_schedule_nominated(self.h, C.byref(cols), pods.n, who,
+                                               out.ctypes.data_as(C.POINTER(abi.KsResult))))
+        out = out[: pods.n]
+        return {"node": out["node"].copy(), "status": out["status"].copy(), "score": out["score"].copy(),
+                "reservation": out["reservation"].copy(), "gpu_minors": out["gpu_minors"].copy(),
+                "rdma_minors": out["rdma_minors"].copy()}
+
+    def stage_nominated(self, pods: PodTable, priority, nominated_node=None, self_id=None):
+        """stage() with the pods' nominations (ks_stage_pods_nominated); schedule_staged() / fetch() follow"""
+        who = self._who_array(pods.n, priority, nominated_node, self_id)
+        cols = pods.ks()
+        self._chk(self.L.ks_stage_pods_nominated(self.h, C.byref(cols), pods.n, who))
+        self.np_staged = pods.n
 
     def checkpoint(self):
         self._chk(self.L.ks_checkpoint(self.h))
