@@ -233,6 +233,11 @@ struct SelectArgs {
   int32_t* next_base;            // NULL = not pipelined
   const int32_t* real_cursor;
   const PodRec* pods;            // a topology pod at the cursor: nothing to select (ks_topo.h)
+  // The dedicated fq commit's pass record (ks_fq.h): per pod the finished FqPod and the raw rows of its top
+  // and second-best nodes.  NULL (every other commit kernel, shards, KS_FQ_STAGED=0) = not written.
+  FqPassRec* fq_rec;             // [64]
+  const uint2* fq_words;         // [total_pods] the per-call FqPod words (prep_fq_words_kernel)
+  const RowCol* rowcols;         // [RF_N]
 };
 
 
@@ -277,6 +282,18 @@ __global__ __launch_bounds__(kSelThreads) void select_kernel(SelectArgs a) {
   const uint2* in = a.in + (size_t)a.c0 * kMaxBatch + p;  // chunk-major sweep output: the pod's column, stride 64
   uint32_t* hist = reinterpret_cast<uint32_t*>(srow + nc);
   uint64_t* xw = reinterpret_cast<uint64_t*>(hist + kSelHistBins);  // [0..3] top, [4..7] cnt | hmax << 32, [8] t | need_eq << 32
+  // the pass record (a.fq_rec): what it takes besides the selection is read here, with the row's first loads -- lane f
+  // of waves 0 and 1 the column of row field f, wave 0 the pod's per-call words and flags
+  RowCol rcol{nullptr, 8, 0};
+  uint2 fqw = make_uint2(0u, 0u);
+  uint32_t pflags = 0;
+  if (a.fq_rec && wv < 2) {
+    rcol = a.rowcols[lane & (RF_N - 1)];
+    if (wv == 0) {
+      fqw = a.fq_words[cursor + p];
+      pflags = a.pods[cursor + p].flags;
+    }
+  }
   int32_t cnt = 0;
   uint32_t hmax = 0;
   uint64_t top = 0;
@@ -329,6 +346,11 @@ __global__ __launch_bounds__(kSelThreads) void select_kernel(SelectArgs a) {
       if (h) atomicAdd(&hist[h], 1u);
     }
     __syncthreads();
+  }
+  if (a.fq_rec && wv == 1 && lane < RF_N) {
+    // the record's top row (the top is known since the first reduction): wave 1, while wave 0 picks the list
+    const int64_t v = load_field(rcol.p, rcol.width, top ? gkey_node(top) : 0);
+    a.fq_rec[p].top[lane] = top ? v : 0;
   }
   if (wv != 0) return;  // waves 1-3 are done
   if (!exhaustive) {
@@ -421,6 +443,33 @@ __global__ __launch_bounds__(kSelThreads) void select_kernel(SelectArgs a) {
     a.cand_top[p] = top;
     a.cand_second[p] = second;
   }
+  if (a.fq_rec) {
+    // the record's second-best row, one field per lane, and the pod's finished FqPod (what the commit's gather
+    // prologue assembles from the words above)
+    FqPassRec* rec = a.fq_rec + p;
+    if (lane < RF_N) {
+      const int64_t v = load_field(rcol.p, rcol.width, second ? gkey_node(second) : 0);
+      rec->run[lane] = second ? v : 0;
+    }
+    if (lane == 0) {
+      FqPod r;
+      r.qmeta = fqw.x;
+      r.flags = pflags;
+      r.qword = fqw.y | ((uint32_t)max(0, min(base, 64)) << 24);
+      r.second = (int32_t)gkey_node(second);
+      r.bound = exhaustive ? 0ull : bound;
+      r.top = top;
+      rec->pod = r;
+    }
+  }
+}
+
+// The per-call FqPod words of every staged pod (ks_fq.h fq_step_words): a function of the pod's quota row and the
+// quota table loaded when the call starts, so it runs in every ks_schedule_staged and is never kept across calls.
+__global__ void prep_fq_words_kernel(const PodRec* pods, const uint32_t* pmask, DevQuotas q, uint2* out, int32_t np) {
+  const int32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= np) return;
+  out[i] = fq_step_words(pods[i].quota, pmask[i], q);
 }
 
 
@@ -1322,6 +1371,11 @@ struct ks_ctx {
   CommitPlan plan;           // the commit kernel's variant and LDS image (ks_plan.h): set by commit_attr_set, then only read
   bool commit_fq = true;     // KS_COMMIT_FQ at ks_create: the dedicated Fit + LoadAware + ElasticQuota commit (ks_fq.h)
   bool fq_keys = true;       // KS_FQ_KEYS at ks_create: that kernel's slot-key table and evaluator wave
+  bool fq_staged = true;     // KS_FQ_STAGED at ks_create: that kernel loads the pass from the select kernel's record
+  bool fq_run = false;       // ... in the current ks_schedule_staged call (schedule_staged_impl)
+  DevPtr<FqPassRec> fq_rec;  // [kMaxBatch] the pass record (allocated by the first call that writes it)
+  DevPtr<uint2> fq_words;    // [fq_words_cap] the per-call FqPod words of the staged queue, rewritten by every call
+  int32_t fq_words_cap = 0;
   // node sharding: shard s = rank * vshards + v owns chunks [s*nchunks/S, (s+1)*nchunks/S)
   int32_t nranks = 1, rank = 0, vshards = 1;
   ncclComm_t comm = nullptr;
@@ -1615,6 +1669,7 @@ int ks_create(const ks_config* cfg, ks_ctx** out) {
   ctx->k = ctx->k_cfg = cfg->candidates > 0 ? std::min(cfg->candidates, kMaxCand) : 32;
   ctx->commit_fq = env_i64("KS_COMMIT_FQ", 1, 0, 1) != 0;  // (per context: a process can build one of each, tests / A-B)
   ctx->fq_keys = env_i64("KS_FQ_KEYS", 1, 0, 1) != 0;
+  ctx->fq_staged = env_i64("KS_FQ_STAGED", 1, 0, 1) != 0;
   if (hipSetDevice(ctx->device) != hipSuccess || hipStreamCreateWithFlags(&ctx->stream.h, hipStreamNonBlocking) != hipSuccess) {
     g_create_error = "ks_create: cannot create HIP stream";
     delete ctx;
@@ -3502,6 +3557,23 @@ static int prep_stage(ks_ctx* ctx, PodStage& st, int32_t p) {
   return KS_OK;
 }
 
+// The dedicated fq commit's staged prologue (ctx->fq_run): the per-call FqPod words of the staged queue, behind
+// prep_stage on the context's stream, and the pass record's buffer.  The words follow the quota table as loaded now.
+static int prep_fq_words(ks_ctx* ctx, PodStage& st, int32_t p) {
+  if (p <= 0) return KS_OK;
+  if (!ctx->fq_rec.get() && dev_alloc(ctx, ctx->fq_rec, (size_t)kMaxBatch * sizeof(FqPassRec)) != KS_OK) return KS_ENOMEM;
+  if (ctx->fq_words_cap < p) {
+    ctx->fq_words_cap = 0;
+    if (dev_alloc(ctx, ctx->fq_words, (size_t)p * sizeof(uint2)) != KS_OK) return KS_ENOMEM;
+    ctx->fq_words_cap = p;
+  }
+  const int threads = 256;
+  hipLaunchKernelGGL(prep_fq_words_kernel, dim3((p + threads - 1) / threads), dim3(threads), 0, ctx->stream,
+                     (const PodRec*)st.recs, (const uint32_t*)st.pq.mask, ctx->quota.q, ctx->fq_words.get(), p);
+  HIPCHK(ctx, hipGetLastError());
+  return KS_OK;
+}
+
 static int validate_pods(ks_ctx* ctx, const ks_pod_cols* pc, int32_t p) {
   if (ctx->cfg.topology.enable) {
     // the CSR lists: monotone offsets from 0, at most KS_TOPO_MAX_TERMS terms per pod, properties / keys in range
@@ -3752,6 +3824,7 @@ static CommitArgs commit_args(ks_ctx* ctx, PodStage& st, int32_t total, int32_t 
   ca.topo_npad = ctx->nodes.npad;
   ca.topo_best = ctx->topo.scr ? &ctx->topo.scr->best_total : nullptr;
   ca.nomq = nullptr;
+  ca.fq_rec = nullptr;
   return ca;
 }
 
@@ -4395,6 +4468,11 @@ static int launch_pass(ks_ctx* ctx, int32_t ppw, int sweep_blocks, const PipeSha
   se.k = ctx->k;
   se.real_cursor = ctx->cursor.get();
   se.pods = ctx->st.recs;
+  // (the record follows the select's cursor word: after a cut pass, and in the re-swept pipeline where the select runs
+  // behind the fix sweep, it is written for the pods the sweep ran for, and a commit at another cursor is a bubble)
+  se.fq_rec = ctx->fq_run ? ctx->fq_rec.get() : nullptr;
+  se.fq_words = ctx->fq_words.get();
+  se.rowcols = ctx->rowcols.get();
   const CandSlot L = cand_slot_layout(ctx->k);
   rec(1, ss);
   for (int32_t v = 0; v < ctx->vshards; ++v) {
@@ -4482,7 +4560,10 @@ static int launch_pass(ks_ctx* ctx, int32_t ppw, int sweep_blocks, const PipeSha
       HIPCHK(ctx, hipGetLastError());
     }
   } else if (plan.mono) HIPCHK(ctx, pl.commit_mono(plan.qcache, plan.mono_smem, cs, ca));
-  else if (plan.fq && !patch) HIPCHK(ctx, fq_launcher(ctx->nodes.nsc).commit(plan.fq_keys, plan.fq_smem, cs, ca));
+  else if (plan.fq && !patch) {
+    ca.fq_rec = se.fq_rec;  // the staged prologue where this pass's select wrote the record
+    HIPCHK(ctx, fq_launcher(ctx->nodes.nsc).commit(plan.fq_keys, plan.fq_smem, cs, ca));
+  }
   else HIPCHK(ctx, pl.commit(plan.qcache, plan.smem, cs, ca));
   rec(2, cs);
   if (pipe) HIPCHK(ctx, hipEventRecord(ctx->pev_com[k % kPipeEvents], cs));
@@ -4590,6 +4671,12 @@ static int schedule_staged_impl(ks_ctx* ctx) {
   HIPCHK(ctx, hipEventRecord(t0, ctx->stream));
   // PreFilter / EstimatePod for the staged queue (the pods' request vectors, estimates, flags)
   if (prep_stage(ctx, ctx->st, np) != KS_OK) return KS_EHIP;
+  // The dedicated fq commit loads its passes from the select kernel's record wherever it runs and the
+  // select kernel finalises the lists: one shard (the merge kernel writes no record).  The patched pipeline and a
+  // nominated table run the general commit; KS_FQ_STAGED=0 keeps the gather prologue (A/B, tests).
+  ctx->fq_run = ctx->fq_staged && ctx->plan.fq && !ctx->plan.mono && !ctx->nom.q_on && S == 1 && !(pipe && pipe->patch);
+  if (ctx->fq_run)
+    if (int rc = prep_fq_words(ctx, ctx->st, np); rc != KS_OK) return rc;
   hipStream_t cs = pipe ? ctx->cstream : ctx->stream;  // where the commits (and the cursor read-back) run
   if (pipe) {
     // the sweep and commit streams start after everything before them on the context's stream

@@ -37,6 +37,50 @@ static_assert(sizeof(FqPod) == 32, "FqPod layout");
 // the records live in the general layout's per-slot NUMA words (kMaxBatch x 32 B), which this plugin set never uses
 static_assert(kMaxBatch == 64 && kMaxCand <= 64 && kQuotaLdsRows < 0xFFFF && KS_QUOTA_DIMS <= 8, "FqPod packing");
 
+// The FqPod words that depend on the pod and the loaded quota table only: written once per ks_schedule_staged call for
+// every pod of the queue (prep_fq_words_kernel, koordgpu.hip), read by the select kernel.
+__device__ __forceinline__ uint2 fq_step_words(int32_t quota, uint32_t pmask, const DevQuotas& q) {
+  uint32_t qmeta = 0xFFFFu;
+  if (quota >= 0) {
+    const int32_t pp = q.parent[quota];
+    qmeta = (uint32_t)(pp < 0 ? 0xFFFF : pp) | ((q.limit_mask[quota] & 0xFFu) << 16) | ((q.min_mask[quota] & 0xFFu) << 24);
+  }
+  return make_uint2(qmeta, (uint32_t)(quota < 0 ? 0xFFFF : quota) | ((pmask & 0xFFu) << 16));
+}
+
+// One pod of a pass as the commit loads it (the staged prologue): the finished FqPod, then the raw rows of the pod's
+// snapshot-best and second-best nodes (zero rows where the node is absent).  Written by select_kernel for the pods at
+// the cursor it read, record p = pod cursor + p, and copied to precs / rawtop / rawrun by a commit at the same cursor.
+struct __attribute__((aligned(16))) FqPassRec {
+  FqPod pod;
+  int64_t top[32], run[32];
+};
+static_assert(sizeof(FqPassRec) == 544 && RF_N == 32, "FqPassRec layout");
+
+// 16 bytes as a native vector (arrays of it stay in registers; HIP's uint4 is a struct around a union)
+typedef uint32_t Quad __attribute__((ext_vector_type(4)));
+
+// A prologue copy in two halves, so that the loads of several copies are all in flight before the first LDS store.
+// No branch around a load (an index past the end re-reads element 0): n >= 1, n <= N * NT.
+template <int N, int NT, typename T>
+struct ProCopy {
+  T v[N];
+  __device__ __forceinline__ void issue(const T* src, int32_t n, int tid) {
+#pragma unroll
+    for (int u = 0; u < N; ++u) {
+      const int32_t i = tid + u * NT;
+      v[u] = src[i < n ? i : 0];
+    }
+  }
+  __device__ __forceinline__ void store(T* dst, int32_t n, int tid) const {
+#pragma unroll
+    for (int u = 0; u < N; ++u) {
+      const int32_t i = tid + u * NT;
+      if (i < n) dst[i] = v[u];
+    }
+  }
+};
+
 // rescan_untouched for this kernel: the node-column pointers are re-read per rescan through an opaque pointer, so
 // the compiler cannot hoist them into SGPRs for the whole loop (rescans are rare)
 template <int NSC>
@@ -123,61 +167,135 @@ __global__ __launch_bounds__(commit_threads(0)) void commit_fq_kernel(CommitArgs
   } while (0)
 #endif
 
-  // ---- load the pass into LDS with every wave (independent loads, one burst) ----
-  lds_copy<NT>(cand_chunk, a.cand_chunk, np * K, tid);
-  lds_copy<NT>(cand_t, a.cand_t, np * K, tid);
-  for (int32_t i = tid; i < np * KS_QUOTA_DIMS; i += NT) {
-    const int32_t p = i / KS_QUOTA_DIMS, dd = i - p * KS_QUOTA_DIMS;
-    pqreq[i] = a.pq.req[dd][cursor0 + p];
-  }
-  {
-    const int64_t* src = reinterpret_cast<const int64_t*>(a.pods + cursor0);
-    int64_t* dst = reinterpret_cast<int64_t*>(spods);
-    const int32_t words = np * (int32_t)(sizeof(PodRec) / 8);
-    lds_copy<NT>(dst, src, words, tid);
-  }
   for (int64_t c = tid; c < a.nchunks; c += NT) touched[c] = 0ull;
-  // raw rows of every pod's snapshot-best node (the fast path's winner) and second-best node (the usual winner of a
-  // pod whose top an earlier pod took): all loads in flight together
-  lds_rawtop<NT>(rawtop, a.cand_top, a.rowcols, np, tid);
-  lds_rawtop<NT>(rawrun, a.cand_second, a.rowcols, np, tid);
-  for (int32_t r = tid; r < a.q.q; r += NT) {
-    qlds->parent[r] = a.q.parent[r];
-    qlds->limit_mask[r] = a.q.limit_mask[r];
-    qlds->min_mask[r] = a.q.min_mask[r];
-  }
-  for (int32_t i = tid; i < a.q.q * KS_QUOTA_DIMS; i += NT) {
-    qlds->limit[i] = a.q.limit[i];
-    qlds->used[i] = a.q.used[i];
-    qlds->min[i] = a.q.min[i];
-    qlds->npused[i] = a.q.npused[i];
-  }
-  // wave 0, lane j: pod j's record
-  if (tid < 64 && lane < np) {
-    const int32_t cnt = a.cand_count[lane];
-    const uint64_t second = a.cand_second[lane];
-    const uint32_t pmask = a.pq.mask[cursor0 + lane];
-    const int32_t quota = a.pods[cursor0 + lane].quota;
-    FqPod r;
-    r.bound = a.cand_bound[lane];
-    r.top = a.cand_top[lane];
-    r.flags = a.pods[cursor0 + lane].flags;
-    r.qmeta = 0xFFFFu;
-    if (quota >= 0) {
-      const int32_t pp = a.q.parent[quota];
-      r.qmeta = (uint32_t)(pp < 0 ? 0xFFFF : pp) | ((a.q.limit_mask[quota] & 0xFFu) << 16) |
-                ((a.q.min_mask[quota] & 0xFFu) << 24);
-    }
-    r.qword = (uint32_t)(quota < 0 ? 0xFFFF : quota) | ((pmask & 0xFFu) << 16) | ((uint32_t)max(0, min(cnt, 64)) << 24);
-    r.second = (int32_t)gkey_node(second);
-    precs[lane] = r;
-  }
-  // lane f < RF_N: the column of row field f
+  // lane f < RF_N: the column of row field f (a miss loads its row through it; read with the prologue's loads, so the
+  // barrier below does not wait for a round trip of its own)
   const void* my_col = nullptr;
   int32_t my_w = 8;
   if (tid < RF_N) {
     my_col = a.rowcols[lane].p;
     my_w = a.rowcols[lane].width;
+  }
+  if (a.fq_rec) {
+    // ---- the staged prologue: the pass's lists, pods, quota requests and quota table, and the record
+    // array the select kernel wrote for the pods at this cursor (FqPassRec: precs, rawtop, rawrun).  Every global
+    // load of the prologue is issued before the first LDS store, so the pass arrives in one round trip behind the
+    // cursor read: nothing here depends on another load. ----
+    constexpr int kRecW = (int)(sizeof(FqPassRec) / 16), kPodW = (int)(sizeof(PodRec) / 16);
+    constexpr int kNL = (kMaxBatch * kMaxCand + NT - 1) / NT, kNQ = (kQuotaLdsRows * KS_QUOTA_DIMS + NT - 1) / NT;
+    constexpr int kNR = (kQuotaLdsRows + NT - 1) / NT, kNP = (kMaxBatch * KS_QUOTA_DIMS + NT - 1) / NT;
+    ProCopy<kNL, NT, uint32_t> c_chunk;
+    ProCopy<kNL, NT, uint2> c_t;
+    ProCopy<(kMaxBatch * kPodW + NT - 1) / NT, NT, Quad> c_pods;
+    ProCopy<(kMaxBatch * kRecW + NT - 1) / NT, NT, Quad> c_rec;
+    ProCopy<kNR, NT, int32_t> c_par;
+    ProCopy<kNR, NT, uint32_t> c_lm, c_mm;
+    ProCopy<kNQ, NT, int64_t> c_lim, c_used, c_min, c_npu;
+    const int32_t nl = np * K, nq = a.q.q, nqd = nq * KS_QUOTA_DIMS, nrec = np * kRecW, npq = np * KS_QUOTA_DIMS;
+    c_rec.issue(reinterpret_cast<const Quad*>(a.fq_rec), nrec, tid);
+    c_chunk.issue(a.cand_chunk, nl, tid);
+    c_t.issue(a.cand_t, nl, tid);
+    c_pods.issue(reinterpret_cast<const Quad*>(a.pods + cursor0), np * kPodW, tid);
+    int64_t rq[kNP];
+    // (the request column by selects over opaque scalar copies of the pointers: indexing the kernel argument by dd
+    // loads the pointer from memory first, a round trip in front of the request's own)
+    const int64_t* qcol[KS_QUOTA_DIMS];
+#pragma unroll
+    for (int d = 0; d < KS_QUOTA_DIMS; ++d) {
+      qcol[d] = a.pq.req[d];
+      asm volatile("" : "+s"(qcol[d]));
+    }
+#pragma unroll
+    for (int u = 0; u < kNP; ++u) {
+      const int32_t i = tid + u * NT, ii = i < npq ? i : 0;
+      const int32_t p = ii / KS_QUOTA_DIMS, dd = ii - p * KS_QUOTA_DIMS;
+      const int64_t* col = qcol[0];
+#pragma unroll
+      for (int d = 1; d < KS_QUOTA_DIMS; ++d) col = dd == d ? qcol[d] : col;
+      rq[u] = gld(col + cursor0 + p);  // (a global load: the opaque copies lost their address space)
+    }
+    c_par.issue(a.q.parent, nq, tid);
+    c_lm.issue(a.q.limit_mask, nq, tid);
+    c_mm.issue(a.q.min_mask, nq, tid);
+    c_lim.issue(a.q.limit, nqd, tid);
+    c_used.issue(a.q.used, nqd, tid);
+    c_min.issue(a.q.min, nqd, tid);
+    c_npu.issue(a.q.npused, nqd, tid);
+    asm volatile("" ::: "memory");  // (no load moves below its copy's stores)
+#pragma unroll
+    for (int u = 0; u < (kMaxBatch * kRecW + NT - 1) / NT; ++u) {
+      const int32_t i = tid + u * NT;
+      if (i < nrec) {
+        const int32_t p = i / kRecW, w = i - p * kRecW;
+        Quad* dst = w < 2    ? reinterpret_cast<Quad*>(precs) + p * 2 + w
+                     : w < 18 ? reinterpret_cast<Quad*>(rawtop) + p * 16 + (w - 2)
+                              : reinterpret_cast<Quad*>(rawrun) + p * 16 + (w - 18);
+        *dst = c_rec.v[u];
+      }
+    }
+    c_chunk.store(cand_chunk, nl, tid);
+    c_t.store(cand_t, nl, tid);
+    c_pods.store(reinterpret_cast<Quad*>(spods), np * kPodW, tid);
+#pragma unroll
+    for (int u = 0; u < kNP; ++u)
+      if (tid + u * NT < npq) pqreq[tid + u * NT] = rq[u];
+    c_par.store(qlds->parent, nq, tid);
+    c_lm.store(qlds->limit_mask, nq, tid);
+    c_mm.store(qlds->min_mask, nq, tid);
+    c_lim.store(qlds->limit, nqd, tid);
+    c_used.store(qlds->used, nqd, tid);
+    c_min.store(qlds->min, nqd, tid);
+    c_npu.store(qlds->npused, nqd, tid);
+  } else {
+    // ---- the gather prologue: the pass's lists and pods, the rows of every pod's top and second-best node from the
+    // node columns, the pods' records assembled by wave 0 (passes without a record) ----
+    lds_copy<NT>(cand_chunk, a.cand_chunk, np * K, tid);
+    lds_copy<NT>(cand_t, a.cand_t, np * K, tid);
+    for (int32_t i = tid; i < np * KS_QUOTA_DIMS; i += NT) {
+      const int32_t p = i / KS_QUOTA_DIMS, dd = i - p * KS_QUOTA_DIMS;
+      pqreq[i] = a.pq.req[dd][cursor0 + p];
+    }
+    {
+      const int64_t* src = reinterpret_cast<const int64_t*>(a.pods + cursor0);
+      int64_t* dst = reinterpret_cast<int64_t*>(spods);
+      const int32_t words = np * (int32_t)(sizeof(PodRec) / 8);
+      lds_copy<NT>(dst, src, words, tid);
+    }
+    // raw rows of every pod's snapshot-best node (the fast path's winner) and second-best node (the usual winner of a
+    // pod whose top an earlier pod took): all loads in flight together
+    lds_rawtop<NT>(rawtop, a.cand_top, a.rowcols, np, tid);
+    lds_rawtop<NT>(rawrun, a.cand_second, a.rowcols, np, tid);
+    for (int32_t r = tid; r < a.q.q; r += NT) {
+      qlds->parent[r] = a.q.parent[r];
+      qlds->limit_mask[r] = a.q.limit_mask[r];
+      qlds->min_mask[r] = a.q.min_mask[r];
+    }
+    for (int32_t i = tid; i < a.q.q * KS_QUOTA_DIMS; i += NT) {
+      qlds->limit[i] = a.q.limit[i];
+      qlds->used[i] = a.q.used[i];
+      qlds->min[i] = a.q.min[i];
+      qlds->npused[i] = a.q.npused[i];
+    }
+    // wave 0, lane j: pod j's record
+    if (tid < 64 && lane < np) {
+      const int32_t cnt = a.cand_count[lane];
+      const uint64_t second = a.cand_second[lane];
+      const uint32_t pmask = a.pq.mask[cursor0 + lane];
+      const int32_t quota = a.pods[cursor0 + lane].quota;
+      FqPod r;
+      r.bound = a.cand_bound[lane];
+      r.top = a.cand_top[lane];
+      r.flags = a.pods[cursor0 + lane].flags;
+      r.qmeta = 0xFFFFu;
+      if (quota >= 0) {
+        const int32_t pp = a.q.parent[quota];
+        r.qmeta = (uint32_t)(pp < 0 ? 0xFFFF : pp) | ((a.q.limit_mask[quota] & 0xFFu) << 16) |
+                  ((a.q.min_mask[quota] & 0xFFu) << 24);
+      }
+      r.qword = (uint32_t)(quota < 0 ? 0xFFFF : quota) | ((pmask & 0xFFu) << 16) | ((uint32_t)max(0, min(cnt, 64)) << 24);
+      r.second = (int32_t)gkey_node(second);
+      precs[lane] = r;
+    }
   }
   if (tid == 0) {
     *hpend = 0;
@@ -597,6 +715,8 @@ __global__ __launch_bounds__(commit_threads(0)) void commit_fq_kernel(CommitArgs
     atomicAdd(&a.counters[15], (unsigned long long)fast);  // ks_stats.diag[7]: monotone fast picks
 #ifdef KS_COMMIT_STAMPS
     for (int i = 0; i < 7; ++i) atomicAdd(&a.counters[8 + i], (unsigned long long)ph[i]);
+#else
+    if (a.fq_rec) atomicAdd(&a.counters[14], 1ull);  // ks_stats.diag[6]: passes loaded by the staged prologue
 #endif
   }
 #undef KS_FSTAMP

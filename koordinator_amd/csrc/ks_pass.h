@@ -424,6 +424,9 @@ struct CommitArgs {
   const long long* topo_best;  // mode 2: the topology step's total of the chosen node
   // the NOM variant only (a nominated table is loaded, ks_nominated.h)
   const DevNomQueue* nomq;
+  // commit_fq_kernel only (ks_fq.h): the pass record the select kernel wrote for the pods at the cursor (FqPassRec
+  // per pod); NULL = the gather prologue (the pass has no record: shards, KS_FQ_STAGED=0)
+  const void* fq_rec;
 };
 
 // NOM: the pods the pass commits -- an owner at the cursor alone, otherwise the pods in front of the first owner
